@@ -11,7 +11,8 @@ then the modq kernel) combines them, overlapped piece by piece with the local wa
 (SHELFI_FHE/dist.py PipelinedCombine; --combine shelfi runs the same combine through
 the library's own C-ABI communicator).  Sharding by ciphertext index instead (every
 rank aggregates all learners' ciphertexts [k0, k1), no collective) is measured in the
-same run and reported as `alternative_partitioning` (--shard cts makes it the headline).
+same run with --full and reported as `alternative_partitioning` (--shard cts makes it the
+headline).
 
 Workload (default): BASELINE config 3's per-GPU shard — 16 learners x ResNet-18
 (11,689,512 params -> 714 ciphertexts of 16384 slots), ring 2^15, L = 4 towers;
@@ -24,7 +25,11 @@ Inputs follow SURVEY §8(d): learner i's vector is
 np.random.default_rng(1000 + i).uniform(-1, 1, n) through float32 (learner i lives on
 rank i mod G), encrypted on device; weights 1/C.
 
-Prints ONE JSON line (rank 0).  Also measured on the same inputs: device-resident
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and
+prints the headline (metric, value, unit, ms_per_step, config); --dump-outputs DIR
+also writes what the last timed step returned (dump_outputs()).  Everything else is
+behind --full: the end-to-end check, the other partitioning / exchange at N > 1, and,
+measured on the same inputs: device-resident
 encode+encrypt and decrypt+decode ms per ciphertext (with their HBM fractions); a
 rocprof-comparable per-launch wavg duration from HIP events (roofline); the bytes
 API sample (PCIe-inclusive); and the CPU baseline (oracle/ port, 1 thread and all
@@ -63,6 +68,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)  # ~0.8 s timed at cfg3: long enough for a 1 s GPU-activity sampler
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every secondary measurement and check: the end-to-end "
+                         "check, per-launch events and the roofline, the untuned output buffer, the other "
+                         "partitioning / exchange at N > 1, encrypt / decrypt times, f4, the bytes API and the "
+                         "CPU baseline (each still has its own switch).  Without it the run sets up, warms up, "
+                         "times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's aggregate "
+                         "residues, a fixed seeded sample of them when they are many) as DIR/<name>.npy, float64")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cfg3")
     ap.add_argument("--learners-per-gpu", type=int, default=0, help="0 = the workload's default")
     ap.add_argument("--pieces", type=int, default=8,
@@ -81,7 +95,7 @@ def parse():
                     help="learner-sharded combine's exchange: sum = uint64 SUM reduce_scatter of the "
                          "partials (+ mod-q fold); packed = the partials written packed (sum_t U_t bits "
                          "per coefficient), an all-to-all, and a local unit-weight sum (DESIGN.md §6). "
-                         "At N > 1 the other one is measured in the same run (alternative_exchange)")
+                         "At N > 1 --full measures the other one in the same run (alternative_exchange)")
     ap.add_argument("--shelfi-fold", action="store_true",
                     help="--combine shelfi: fold each piece mod q after its collective (default: leave "
                          "the sums to the consumer, shelfi_dev_decrypt_sum folds them on load)")
@@ -99,7 +113,7 @@ def parse():
     ap.add_argument("--force-dist", action="store_true",
                     help="use the N>1 path (NCCL group, pipelined reduce_scatter, modq) even at N=1")
     ap.add_argument("--no-alt", action="store_true",
-                    help="N>1: skip measuring the other partitioning in the same run")
+                    help="--full at N>1: skip measuring the other partitioning in the same run")
     ap.add_argument("--no-check", action="store_true",
                     help="skip the end-to-end check (decrypt of owned aggregate cts vs plain FedAvg)")
     ap.add_argument("--comm-check", action="store_true",
@@ -133,7 +147,10 @@ def parse():
     ap.add_argument("--encdec-valu-json", default=os.path.join(ROOT, "profiles", "encdec_valu.json"),
                     help="SQ_INSTS_VALU wave-instructions per ciphertext of the encrypt / decrypt chains "
                          "(tools/encdec_valu.py over tools/encdec_prof.py, cfg3 parameters)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 class ShelfiCombine:
@@ -204,6 +221,36 @@ def check_owned(ck, D, owned, world, Cl, params, batch, delta, max_cts=8, terms=
         n_checked += b - a
     return {"max_abs_err": err, "cts_checked_per_rank": n_checked,
             "what": "decrypt(aggregate) vs plain FedAvg of all %d learners" % total}
+
+
+DUMP_SAMPLE = 1 << 21  # residues written by --dump-outputs: three float64 arrays of this many, ~50 MB
+
+
+def dump_outputs(owned, path):
+    """--dump-outputs: what the last timed step returned, `owned` = [(a, b, residues of the aggregate
+    ciphertexts [a, b))], flattened in that order.  The residues are uint64 (up to 60 bits), so each is
+    written exactly as two float64 values: aggregate_lo32.npy (its low 32 bits) and aggregate_hi.npy (the
+    rest); aggregate_index.npy holds each one's flat index.  More than DUMP_SAMPLE residues (cfg3: 187 M)
+    are sampled at default_rng(0)'s indices, the same from run to run."""
+    import numpy as np
+    import torch
+
+    total = sum(s.numel() for _, _, s in owned)
+    if total > DUMP_SAMPLE:
+        idx = np.unique(np.random.default_rng(0).integers(0, total, DUMP_SAMPLE))
+    else:
+        idx = np.arange(total, dtype=np.int64)
+    vals, off = [], 0
+    for _, _, s in owned:
+        flat = s.reshape(-1)
+        sel = idx[(idx >= off) & (idx < off + flat.numel())] - off
+        vals.append(flat[torch.from_numpy(sel).to(flat.device)].cpu().numpy())
+        off += flat.numel()
+    v = (np.concatenate(vals) if vals else np.zeros(0, np.int64)).view(np.uint64)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "aggregate_lo32.npy"), (v & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(path, "aggregate_hi.npy"), (v >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(path, "aggregate_index.npy"), idx.astype(np.float64))
 
 
 def _median_rate(fn, units, seconds, parts=5):
@@ -500,13 +547,15 @@ def main():
                 "cts": cts, "placement": placement, "make_comb": make_comb, "step_of": step_of,
                 "arena_layout": arena.layout}
 
-    def timed(mode):
+    def timed(mode, dump=None):
         """warmup, then exactly `steps` steps between barrier + sync; max over ranks.
         Two HIP events on the launch stream (torch's current stream) bracket the timed
         steps: without a collective their span / steps is the average wavg launch over the
         timed region (back-to-back launches, boundaries included).  Per-launch events
-        (min, spread) come from a second pass outside the timed region: recorded around
-        every launch inside it, they cost more host time than a cfg2 launch takes."""
+        (min, spread) come from a second pass outside the timed region (--full only): recorded
+        around every launch inside it, they cost more host time than a cfg2 launch takes.
+        The last value returned is what the last timed step returned (--dump-outputs)."""
+        last = None
         for _ in range(args.warmup):
             mode["step"]()
         torch.cuda.synchronize()
@@ -521,7 +570,7 @@ def main():
             if mode["comb"] is None:
                 mode["kernel"]()
             else:
-                mode["step"]()
+                last = mode["step"]()
         region[1].record(stream)
         torch.cuda.synchronize()
         if distributed:
@@ -529,19 +578,27 @@ def main():
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         region_avg = region[0].elapsed_time(region[1]) / args.steps if mode["comb"] is None else None
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-              for _ in range(args.steps)]
-        for i in range(args.steps):  # the local kernel alone, outside the timed region
-            ev[i][0].record(stream)
-            mode["kernel"]()
-            ev[i][1].record(stream)
-        torch.cuda.synchronize()
+        if mode["comb"] is None:  # the launches wrote the step's one output buffer
+            last = [(mode["k_lo"], mode["k_hi"], mode["out"])]
+        if dump and rank == 0:
+            dump_outputs(last, dump)  # before any later launch reuses the buffers
+        per = None
+        if args.full:
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                  for _ in range(args.steps)]
+            for i in range(args.steps):  # the local kernel alone, outside the timed region
+                ev[i][0].record(stream)
+                mode["kernel"]()
+                ev[i][1].record(stream)
+            torch.cuda.synchronize()
+            per = sorted(a.elapsed_time(b) for a, b in ev)
         if distributed:
             tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = tt.item()
-        per = sorted(a.elapsed_time(b) for a, b in ev)
-        return elapsed, (region_avg if region_avg is not None else sum(per) / len(per)), per
+        if region_avg is None and per:
+            region_avg = sum(per) / len(per)
+        return elapsed, region_avg, per
 
     def checked(mode):
         """End to end: this rank's owned aggregate cts (after the collective + modq in
@@ -560,10 +617,45 @@ def main():
 
     units = Cl * world * K  # client ciphertexts folded per step, whole job (any shard)
     main_mode = build(args.shard if distributed else "local")
-    elapsed, kern_avg_ms, kern_ms = timed(main_mode)
+    elapsed, kern_avg_ms, kern_ms = timed(main_mode, dump=args.dump_outputs)
     ms_per_step = elapsed * 1e3 / args.steps
     value = units / (elapsed / args.steps)
-    check = None if args.no_check else checked(main_mode)
+    cts_mode = main_mode["shard"] == "cts"
+    # the headline line: all a run without --full computes
+    res = {
+        "metric": METRIC, "value": round(value, 1), "unit": "client-ciphertexts/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64",
+        "data": "synthetic: real CKKS encryptions (device encoder + ChaCha20 sampler) of "
+                "default_rng(1000+i).uniform(-1,1) float32 vectors; inputs resident in HBM before "
+                "the timed region",
+        "config": {"workload": "%s: %d learners/GPU x %s (%d params -> %d cts of %d slots), ring 2^%d, "
+                               "L=%d towers%s" % (args.workload, Cl, model, params, K, batch,
+                                                  N.bit_length() - 1, L,
+                                                  "" if not distributed else
+                                                  (", ciphertext-sharded: each rank aggregates all %d learners' "
+                                                   "cts [k0, k1), no collective" % (Cl * world)) if cts_mode else
+                                                  (", RCCL reduce_scatter overlapped in %d pieces" % args.pieces
+                                                   if args.combine == "torch" else
+                                                   ", RCCL reduce_scatter overlapped in %d pieces inside libshelfi "
+                                                   "(shelfi_dev_combine_arena, mod-q fold %s)"
+                                                   % (args.pieces, "per piece" if args.shelfi_fold else
+                                                      "in the consumer's decrypt"))),
+                   "ring_dim": N, "towers": L, "learners_total": Cl * world, "cts_per_learner": K,
+                   "parallelism": ("dp1 (one GPU, no collective)" if not distributed else
+                                   "ciphertext-sharded dp%d (no collective)" % world if cts_mode else
+                                   "learner-sharded dp%d + RCCL reduce_scatter over xGMI + modq" % world
+                                   if args.combine == "torch" or args.shelfi_fold else
+                                   "learner-sharded dp%d + RCCL reduce_scatter over xGMI (C ABI; fold in decrypt)"
+                                   % world),
+                   "layout": args.layout, "output_placement": main_mode["placement"],
+                   "exchange": None if not distributed or cts_mode else
+                   ("uint64 SUM reduce_scatter" if args.exchange == "sum" else
+                    "packed partials (sum_t U_t bits/coeff) all-to-all + unit-weight sum")},
+    }
+    if args.dump_outputs:
+        res["outputs_dumped"] = ["aggregate_lo32", "aggregate_hi", "aggregate_index"]
+    check = checked(main_mode) if args.full and not args.no_check else None
     # the library's own C-ABI communicator (comm.cpp: RCCL uint64 SUM + mod-q fold inside
     # libshelfi) on the same partial sums, outside the timed region: its all-reduced
     # aggregate must equal the torch path's owned shares bit for bit on every rank.  It runs
@@ -604,6 +696,42 @@ def main():
             return {"ok": bool(okt.item()), "seconds": round(time.perf_counter() - t0, 3), "what": what}
         except Exception as e:  # reported, never fatal to the headline
             return {"ok": False, "error": repr(e)[:300]}
+
+    def finish():
+        """Write the one JSON line (rank 0) and leave the process group; at N > 1 under a
+        watchdog, with the opt-in C-ABI communicator check before the line."""
+        emit_lock = threading.Lock()
+        emitted = []
+
+        def emit():
+            with emit_lock:
+                if rank == 0 and not emitted:
+                    emitted.append(1)
+                    os.write(json_fd, (json.dumps(res) + "\n").encode())
+
+        finished = threading.Event()
+        if distributed:
+            dist.barrier()  # rank 0 ran the f4 / bytes-API samples alone: start every watchdog together
+
+            def watchdog():
+                if not finished.wait(COMM_CHECK_TIMEOUT_S):
+                    res["c_abi_comm_check" if args.comm_check else "final_barrier"] = {
+                        "ok": False, "error": "no result within %d s; exited with status %d"
+                        % (COMM_CHECK_TIMEOUT_S, COMM_HANG_EXIT)}
+                    emit()
+                    os._exit(COMM_HANG_EXIT)  # the line is written, but a hung collective fails the run
+            threading.Thread(target=watchdog, daemon=True).start()
+            if main_mode["shard"] == "learners" and args.comm_check:
+                res["c_abi_comm_check"] = c_abi_comm_check()
+        emit()
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        finished.set()
+
+    if not args.full:
+        finish()
+        return
 
     # the same launches into a plain torch.empty output (no placement tuning): the
     # kernel's placement-independent rate (DESIGN.md §5.2)
@@ -659,7 +787,6 @@ def main():
         torch.cuda.empty_cache()
     out, K_loc, C_loc = main_mode["out"], main_mode["K_loc"], main_mode["C_loc"]
     enc_times, cts, weights = main_mode["enc_times"], main_mode["cts"], main_mode["weights"]
-    cts_mode = main_mode["shard"] == "cts"
     local_wavg = main_mode["kernel"]
 
     # device-resident decrypt+decode timing over the K aggregated ciphertexts: the exact
@@ -903,36 +1030,7 @@ def main():
     def frac(bytes_, ms):
         return round(bytes_ / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
 
-    res = {
-        "metric": METRIC, "value": round(value, 1), "unit": "client-ciphertexts/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64",
-        "data": "synthetic: real CKKS encryptions (device encoder + ChaCha20 sampler) of "
-                "default_rng(1000+i).uniform(-1,1) float32 vectors; inputs resident in HBM before "
-                "the timed region",
-        "config": {"workload": "%s: %d learners/GPU x %s (%d params -> %d cts of %d slots), ring 2^%d, "
-                               "L=%d towers%s" % (args.workload, Cl, model, params, K, batch,
-                                                  N.bit_length() - 1, L,
-                                                  "" if not distributed else
-                                                  (", ciphertext-sharded: each rank aggregates all %d learners' "
-                                                   "cts [k0, k1), no collective" % (Cl * world)) if cts_mode else
-                                                  (", RCCL reduce_scatter overlapped in %d pieces" % args.pieces
-                                                   if args.combine == "torch" else
-                                                   ", RCCL reduce_scatter overlapped in %d pieces inside libshelfi "
-                                                   "(shelfi_dev_combine_arena, mod-q fold %s)"
-                                                   % (args.pieces, "per piece" if args.shelfi_fold else
-                                                      "in the consumer's decrypt"))),
-                   "ring_dim": N, "towers": L, "learners_total": Cl * world, "cts_per_learner": K,
-                   "parallelism": ("dp1 (one GPU, no collective)" if not distributed else
-                                   "ciphertext-sharded dp%d (no collective)" % world if cts_mode else
-                                   "learner-sharded dp%d + RCCL reduce_scatter over xGMI + modq" % world
-                                   if args.combine == "torch" or args.shelfi_fold else
-                                   "learner-sharded dp%d + RCCL reduce_scatter over xGMI (C ABI; fold in decrypt)"
-                                   % world),
-                   "layout": args.layout, "output_placement": main_mode["placement"],
-                   "exchange": None if not distributed or cts_mode else
-                   ("uint64 SUM reduce_scatter" if args.exchange == "sum" else
-                    "packed partials (sum_t U_t bits/coeff) all-to-all + unit-weight sum")},
+    res.update({
         "roofline": roofline,
         "encode_encrypt_ms_per_ct": round(enc_ms, 5),
         "encode_encrypt_per_learner_call_ms_per_ct": round(enc_first_ms, 5),
@@ -940,7 +1038,7 @@ def main():
         "decrypt_decode_flooded_ms_per_ct": round(dec_flood_ms_per_ct, 5),
         "encrypt_hbm_frac": frac(enc_bytes, enc_ms),
         "decrypt_hbm_frac": frac(dec_bytes, dec_ms_per_ct),
-    }
+    })
     # the counter files are per parameter set: 2^15 / L4 (cfg2 / cfg3 / cfg5) in the named files, 2^16 / L6
     # (cfg4, round 6) in their "_cfg4" siblings (tools/profile_cfg4_r06.sh, K = 32 as the steady loop here)
     def wl_json(path):
@@ -1010,34 +1108,7 @@ def main():
         res["f4_eval_mult"] = f4
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(N, L, q, psi, delta, batch, Cl, args.cpu_seconds)
-    emit_lock = threading.Lock()
-    emitted = []
-
-    def emit():
-        with emit_lock:
-            if rank == 0 and not emitted:
-                emitted.append(1)
-                os.write(json_fd, (json.dumps(res) + "\n").encode())
-
-    finished = threading.Event()
-    if distributed:
-        dist.barrier()  # rank 0 ran the f4 / bytes-API samples alone: start every watchdog together
-
-        def watchdog():
-            if not finished.wait(COMM_CHECK_TIMEOUT_S):
-                res["c_abi_comm_check" if args.comm_check else "final_barrier"] = {
-                    "ok": False, "error": "no result within %d s; exited with status %d"
-                    % (COMM_CHECK_TIMEOUT_S, COMM_HANG_EXIT)}
-                emit()
-                os._exit(COMM_HANG_EXIT)  # the line is written, but a hung collective fails the run
-        threading.Thread(target=watchdog, daemon=True).start()
-        if main_mode["shard"] == "learners" and args.comm_check:
-            res["c_abi_comm_check"] = c_abi_comm_check()
-    emit()
-    if distributed:
-        dist.barrier()
-        dist.destroy_process_group()
-    finished.set()
+    finish()
 
 
 if __name__ == "__main__":

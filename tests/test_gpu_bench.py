@@ -30,7 +30,38 @@ def _port():
         return s.getsockname()[1]
 
 
-COMMON = ["--workload", "cfg2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--api-cts", "4"]
+PLAIN = ["--workload", "cfg2", "--steps", "3", "--warmup", "1"]
+# the secondary measurements and bench's own end-to-end check run with --full only
+COMMON = PLAIN + ["--full", "--no-cpu-baseline", "--api-cts", "4"]
+
+
+def test_bench_plain_run_headline_and_dump(tmp_path):
+    """Without --full: the headline line alone, none of the secondary keys; --dump-outputs writes the
+    last timed step's aggregate residues (cfg2: 4 cts x 2 x 4 towers x 2^15, all of them) as float64
+    halves that recombine to residues below their moduli, the same in a second run."""
+    import numpy as np
+
+    runs = []
+    for name in ("a", "b"):
+        d = str(tmp_path / name)
+        r = _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", d] + PLAIN)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "config"):
+            assert k in r, k
+        assert r["steps"] == 3 and r["value"] > 0 and r["ms_per_step"] > 0
+        for k in ("roofline", "check", "cpu_baseline", "api_bytes_path", "f4_eval_mult",
+                  "encode_encrypt_ms_per_ct", "decrypt_decode_ms_per_ct"):
+            assert k not in r, k
+        arrs = {n: np.load(os.path.join(d, n + ".npy")) for n in r["outputs_dumped"]}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        runs.append(arrs)
+    a, b = runs
+    n = 4 * 2 * 4 * (1 << 15)
+    assert np.array_equal(a["aggregate_index"], np.arange(n))
+    res = (a["aggregate_hi"].astype(np.uint64) << np.uint64(32)) | a["aggregate_lo32"].astype(np.uint64)
+    assert res.max() < (1 << 60) and len(np.unique(res)) > n // 2  # residues, not a cleared buffer
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
 
 
 def test_bench_single_gpu_line():

@@ -9,4 +9,4 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 out=gpurun_out/profile_$tag
 mkdir -p "$out"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o "$tag" \
-  -- /usr/bin/python3 bench.py > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
+  -- "$(command -v python3)" bench.py --full > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"

@@ -7,6 +7,7 @@
 #   tools/scale_recipe.sh 8 --combine shelfi     # the same pipelined combine inside libshelfi (C ABI)
 #   tools/scale_recipe.sh 8 --shard cts          # ciphertext-sharded, no collective
 #   tools/scale_recipe.sh 8 --comm-check         # + cross-check of the C-ABI communicator (opt-in)
+#   tools/scale_recipe.sh 8 --full               # + end-to-end check, the other partitioning / exchange, secondary numbers
 set -euo pipefail
 N=${1:-8}
 shift || true

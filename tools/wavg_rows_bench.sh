@@ -5,7 +5,7 @@
 set -euo pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/wavg_rows_bench
-B="--steps 100 --warmup 3 --no-cpu-baseline --api-cts 0 --no-check --f4-cts 0 --no-alt"
+B="--full --steps 100 --warmup 3 --no-cpu-baseline --api-cts 0 --no-check --f4-cts 0 --no-alt"
 for rnd in 1 2; do
   for wl in $1; do
     vs="$2"
