@@ -1,0 +1,168 @@
+// api_internal.h — declarations shared by the C-ABI sources only (context.cpp, wire.cpp, call_state.cpp,
+// bytes_api.cpp, dev_api.cpp).  The contract with the kernels, eval.cpp and comm.cpp is shelfi_internal.h.
+#pragma once
+
+#include <string.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "host_stage.h"
+#include "shelfi_internal.h"
+
+// Nothing declared here is part of libshelfi.so's dynamic symbol table.
+#pragma GCC visibility push(hidden)
+
+namespace shelfi {
+
+// ---------------------------------------------------------- context.cpp ----
+// encryption/keygen stream key + first ciphertext index for this call
+void draw_key(shelfi_ctx* ctx, uint64_t count, uint32_t key[8], uint64_t* g0);
+
+// Zeroes a call's stream key when the call leaves its scope, by return or by exception.
+struct KeyWiper {
+  uint32_t* key;
+  explicit KeyWiper(uint32_t k[8]) : key(k) {}
+  ~KeyWiper() { explicit_bzero(key, 8 * sizeof(uint32_t)); }
+  KeyWiper(const KeyWiper&) = delete;
+  KeyWiper& operator=(const KeyWiper&) = delete;
+};
+
+// ------------------------------------------------------------- wire.cpp ----
+// 64-byte little-endian header followed by K x 2 x L x N uint64 residues in the
+// device layout [ct][poly][tower][coeff] (EVALUATION, PALISADE bit-reversed order).
+struct BlobHeader {
+  char magic[4];           // "SHCT"
+  uint16_t version;        // 1
+  uint16_t header_bytes;   // 64
+  uint32_t logN;
+  uint32_t L;
+  uint64_t K;              // ciphertexts in the blob
+  uint32_t depth;          // PALISADE depth (1 fresh, 2 after EvalMult by constant)
+  uint32_t level;          // always 0 (no rescale on this path)
+  double scale;            // scaling factor (Delta for fresh, Delta^2 after EvalMult)
+  uint64_t params_id;      // hash of (N, L, q)
+  uint64_t key_id;         // hash of the public key (PALISADE keyTag analogue)
+  uint32_t batch;          // slots per ciphertext
+  uint32_t encoding;       // 4 = CKKSPacked (PALISADE PlaintextEncodings)
+};
+static_assert(sizeof(BlobHeader) == 64, "blob header must be 64 bytes");
+
+// Packed wire payload sizes (version-2 blobs): bytes of one (ct, poly) group of the first Lu towers.
+uint64_t packed_poly_bytes(const Params& p, uint32_t Lu);
+// The widths of the first Lu towers (the buffers a prefix upload unpacks)
+ArenaPack arena_pack_prefix(const Params& p, uint32_t Lu);
+
+// Where the residues of a bytes-API ciphertext batch live in host memory: a library
+// blob (one contiguous payload) or a PALISADE archive (2*L tower runs per ciphertext,
+// palisade_codec.h).  Both map onto the device layout [K][2][L][N].
+struct CtLayout {
+  uint8_t* base = nullptr;
+  bool pal = false;
+  bool packed = false;  // a version-2 (packed) library blob
+  int fmt() const { return pal ? 1 : packed ? 2 : 0; }  // shelfi_set_wire_format's numbering
+  uint64_t K = 0;
+  uint32_t depth = 0;
+  uint64_t level = 0;
+  double scale = 0.0;
+  std::vector<size_t> off;  // PALISADE tower offsets [K][2][L]
+  // ciphertexts [k0, k0 + kn) as host pieces in [K][2][L][N] order; with Lu < L only each
+  // polynomial's first Lu towers (the decode's prefix, decode_pass): [kn][2][Lu][N]
+  void pieces(uint64_t k0, uint64_t kn, const Params& p, std::vector<HostPiece>& out, uint32_t Lu = 0) const {
+    out.clear();
+    if (!Lu) Lu = p.L;
+    const size_t poly_bytes = (size_t)p.L * p.N * 8, ct_bytes = 2 * poly_bytes;
+    if (packed) {  // (ct, poly) groups of packed rows; a tower prefix is a prefix of each group
+      const uint64_t pg = packed_poly_bytes(p, p.L);
+      if (Lu == p.L) {
+        out.push_back(HostPiece{base + sizeof(BlobHeader) + k0 * 2 * pg, kn * 2 * pg});
+        return;
+      }
+      const uint64_t pl = packed_poly_bytes(p, Lu);
+      for (uint64_t i = 2 * k0; i < 2 * (k0 + kn); ++i)
+        out.push_back(HostPiece{base + sizeof(BlobHeader) + i * pg, (size_t)pl});
+      return;
+    }
+    if (!pal) {
+      if (Lu == p.L) {
+        out.push_back(HostPiece{base + sizeof(BlobHeader) + k0 * ct_bytes, kn * ct_bytes});
+        return;
+      }
+      for (uint64_t i = 2 * k0; i < 2 * (k0 + kn); ++i)
+        out.push_back(HostPiece{base + sizeof(BlobHeader) + i * poly_bytes, (size_t)Lu * p.N * 8});
+      return;
+    }
+    for (uint64_t i = 2 * k0; i < 2 * (k0 + kn); ++i)
+      for (uint32_t t = 0; t < Lu; ++t) out.push_back(HostPiece{base + off[i * p.L + t], (size_t)p.N * 8});
+  }
+};
+
+// A caller's ciphertext batch, validated against the context (params and key).
+CtLayout open_cts(const shelfi_ctx* ctx, const uint8_t* b, size_t len);
+// Size of (and, with buf, the header / framing of) an output batch in format fmt; returns its layout.
+CtLayout make_output(const shelfi_ctx* ctx, int fmt, uint64_t K, uint32_t depth, uint64_t level, double scale,
+                     uint8_t* buf, size_t* total);
+
+// -------------------------------------------------------- bytes_api.cpp ----
+// The ctx's pinned staging rings, created on first use
+Stager& stager(shelfi_ctx* ctx);
+
+// Drops the staged outputs of a pipeline that threw (declared after its Pipe, so the
+// slots are abandoned before the streams are drained).
+struct StageRun {
+  Stager& s;
+  bool done = false;
+  explicit StageRun(Stager& st) : s(st) { s.begin(); }
+  void finish() {
+    s.finish();
+    done = true;
+  }
+  ~StageRun() {
+    if (!done) s.abort();
+  }
+};
+
+// ------------------------------------------------------- call_state.cpp ----
+// W = (int64)((double)(float)w * Delta + 0.5) mod q_t as two 30-bit limbs, wl[t][2] for the p.L towers
+void weight_limbs(float w, const Params& p, uint32_t* wl);
+// the same for the n learners of a wavg launch
+void fill_weights(WavgArgs& a, const Params& p, const float* w, size_t n);
+
+GenFlag next_gen_flag(shelfi_ctx* ctx);
+// after the call's synchronisation: did it raise word w?
+bool gen_flag_raised(const shelfi_ctx* ctx, const GenFlag& f, int w);
+bool encode_needs_approx(const shelfi_ctx* ctx, const GenFlag& f);
+
+DecodeNoise decode_noise_begin(shelfi_ctx* ctx, uint64_t K, const GenFlag& fl);
+void decode_noise_readback(shelfi_ctx* ctx, const DecodeNoise& dn);
+void decode_noise_end(shelfi_ctx* ctx, const DecodeNoise& dn);
+
+// One pass of a decrypt call over ciphertexts of `towers` towers: the parameters and tables of the
+// towers it decodes with -- the fast CRT's prefix (decode_towers), or (exact) every tower.
+struct DecodePass {
+  Params p;
+  const DeviceTables& dt;
+};
+DecodePass decode_pass(shelfi_ctx* ctx, uint32_t towers, bool exact);
+
+// The passes of a decrypt call: run(exact) enqueues one pass over the whole call, wait() returns once
+// that pass has completed.  The fast pass first; when it met a coefficient outside the fast CRT's
+// range (GenFlag word 2), the call again, exactly.  Then the flooding's precision verdict; the
+// flooding key is wiped however the call ends.
+template <class Run, class Wait>
+void decrypt_passes(shelfi_ctx* ctx, const GenFlag& fl, DecodeNoise& dn, Run run, Wait wait) {
+  KeyWiper wipe(dn.key);
+  if (ctx->decode_exact) {
+    run(true);
+  } else {
+    run(false);
+    wait();
+    if (gen_flag_raised(ctx, fl, 2)) run(true);
+  }
+  wait();
+  decode_noise_end(ctx, dn);
+}
+
+}  // namespace shelfi
+
+#pragma GCC visibility pop

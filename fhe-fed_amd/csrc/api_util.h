@@ -1,4 +1,5 @@
-// api_util.h — host helpers shared by the C-ABI sources (api.cpp, eval.cpp).
+// api_util.h — host helpers shared by the C-ABI sources (context.cpp, wire.cpp, call_state.cpp,
+// bytes_api.cpp, dev_api.cpp, eval.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>

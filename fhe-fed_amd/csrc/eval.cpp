@@ -226,7 +226,7 @@ static LevelState& level(shelfi_ctx* ctx, uint32_t Ll) {
   return l;
 }
 
-// tables of Q_l for decrypt at a level (api.cpp): the Q_l tables alone
+// tables of Q_l for decrypt at a level (call_state.cpp decode_pass): the Q_l tables alone
 const DeviceTables& level_tables(shelfi_ctx* ctx, uint32_t Ll) { return level_q(ctx, Ll); }
 
 static void install_evk(shelfi_ctx* ctx, EvalState& ev, const uint64_t* evk) {

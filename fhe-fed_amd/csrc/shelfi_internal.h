@@ -57,7 +57,7 @@ inline uint32_t ntt_block_log(uint32_t logN) {
 
 // A/B probe switches (none changes an output bit), process-wide: read from the
 // environment when a context is created and by shelfi_reload_switches() -- never on a launch path --
-// and published as an immutable snapshot (api.cpp), so concurrent calls never see a torn struct.
+// and published as an immutable snapshot (switches.cpp), so concurrent calls never see a torn struct.
 struct Switches {
   bool xcd_order = true;       // SHELFI_XCD_ORDER=0: natural block order in the NTT block passes
   bool ntt_wl = true;          // SHELFI_NTT_WL=0: a workgroup barrier at every block-pass exchange
@@ -179,7 +179,7 @@ struct DeviceTables {
 };
 constexpr int kCrtMwMaxLimbs = 36;  // crt_exact_kernel: 16 towers below 2^60, times L, plus sign
 
-// NTT / CRT tables of an arbitrary tower list p.q[0..p.L) (api.cpp); free_ntt_tables frees
+// NTT / CRT tables of an arbitrary tower list p.q[0..p.L) (context.cpp); free_ntt_tables frees
 // only what build_ntt_tables allocates (not the FFT / Gaussian tables of a context).
 void build_ntt_tables(const Params& p, DeviceTables& dt);
 void free_ntt_tables(DeviceTables& dt);
@@ -310,7 +310,7 @@ struct ArenaPack {
   uint32_t pre[kMaxTowers];  // sum of U_t' for t' < t
   uint32_t sum;              // sum of U_t
 };
-ArenaPack arena_pack(const Params& p);                 // api.cpp
+ArenaPack arena_pack(const Params& p);                 // dev_api.cpp
 uint64_t arena_ct_words(const Params& p, uint64_t C);  // uint64 words per ciphertext of C learners
 // sum_c W_c x_c over C learners (any C: groups of 16 folded into a running sum), weight limbs
 // wl_dev [C][L][2]; rows = K * 2 * L ciphertext polynomials
@@ -390,7 +390,8 @@ void launch_keygen(const Params& p, const DeviceTables& dt, const uint32_t key[8
                    uint64_t* pk, void* scratch, hipStream_t s);
 size_t keygen_scratch_bytes(const Params& p);
 
-// api.cpp: the arena aggregation (ctx lock held, weights checked), refused-slot check, weights
+// dev_api.cpp: the arena aggregation (ctx lock held, weights checked), refused-slot check;
+// call_state.cpp: weights
 void wavg_arena_enqueue(shelfi_ctx* ctx, const uint64_t* arena_dev, const float* w, size_t C, size_t K,
                         uint64_t* out_dev, hipStream_t s);
 void wavg_arena_enqueue_packed(shelfi_ctx* ctx, const uint64_t* arena_dev, const float* w, size_t C, size_t K,
@@ -407,7 +408,7 @@ void eval_release(shelfi_ctx* ctx, bool keys_only);
 void load_evalkey_if_present(shelfi_ctx* ctx, const std::string& dir);
 // eval.cpp: NTT / CRT tables of Q_l (towers q_0 .. q_{Ll-1}) for decrypt at a level
 const DeviceTables& level_tables(shelfi_ctx* ctx, uint32_t Ll);
-// api.cpp helpers shared with eval.cpp
+// context.cpp helpers shared with eval.cpp
 void seed_to_key(uint64_t seed, uint32_t key[8]);
 void os_random(void* buf, size_t n);
 void require_keys(const shelfi_ctx* ctx);

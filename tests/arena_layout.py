@@ -1,5 +1,5 @@
 """numpy restatement of the packed arena's documented layout (kernels.hip 'packed
-arena'): the width rule of arena_pack (api.cpp) and the row / slice / plane geometry of
+arena'): the width rule of arena_pack (dev_api.cpp) and the row / slice / plane geometry of
 arena_pack_kernel and wavg_packed.  Test infrastructure: the GPU test compares the device arena's
 words with pack_arena(); the CPU test round-trips pack_arena() / unpack_arena()."""
 import numpy as np
@@ -7,7 +7,7 @@ import numpy as np
 
 def widths(q):
     """U_t per tower: bitlength(q_t) when that is 1 mod 4 (a 4-multiple field + a flag plane),
-    else rounded up to a multiple of 4; at least 32 (api.cpp arena_pack)."""
+    else rounded up to a multiple of 4; at least 32 (dev_api.cpp arena_pack)."""
     out = []
     for x in q:
         b = int(x).bit_length()

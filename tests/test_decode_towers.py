@@ -2,7 +2,7 @@
 checked on the CPU with Python integers against the oracle's exact centred CRT.
 
 The kernel (`crt_value`, kernels.hip) decodes with the shortest prefix of q_0.. whose product Q'
-exceeds 2^130 (`decode_towers`, api.cpp): y_t = r_t (Q'/q_t)^-1 mod q_t, k = round(sum_t y_t / q_t)
+exceeds 2^130 (`decode_towers`, call_state.cpp): y_t = r_t (Q'/q_t)^-1 mod q_t, k = round(sum_t y_t / q_t)
 from binary32 terms (y_t >> s_t) * (2^s_t / q_t) (s_t = max(0, bitlen(q_t) - 32)), and
 X = sum_t y_t (Q'/q_t) - k Q' mod 2^128 read as a signed 128-bit integer.  For every |X| < 2^127
 (the range the 128-bit decode represents) that must be X itself — the value the oracle's
@@ -28,7 +28,7 @@ def _decode_towers(q):
 
 
 def _crt_nc(q):
-    """api.cpp build_ntt_tables: columns for |X'| < L Q' plus a sign bit (0 = exact path only)."""
+    """context.cpp build_ntt_tables: columns for |X'| < L Q' plus a sign bit (0 = exact path only)."""
     qbits = sum(int(v).bit_length() for v in q)
     need = qbits + len(q).bit_length() + 1
     nc = max(5, -(-need // 30))

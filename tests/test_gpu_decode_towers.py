@@ -1,4 +1,4 @@
-"""Decrypt decodes with the shortest tower prefix whose modulus exceeds 2^130 (api.cpp
+"""Decrypt decodes with the shortest tower prefix whose modulus exceeds 2^130 (call_state.cpp
 decode_towers): for every value the 128-bit decode represents (|X| < 2^127)
 the centred CRT over that prefix is X itself, so the dropped towers change no output bit.
 Checked here bit for bit against the all-tower decode (SHELFI_DEC_ALL_TOWERS=1, read per call)

@@ -519,7 +519,7 @@ def test_no_getenv_on_a_launch_path():
     import re
 
     csrc = os.path.join(ROOT, "fhe-fed_amd", "csrc")
-    allowed = {"api.cpp": {"env_flag", "env_choice", "reload_switches"}, "host_stage.cpp": None,
+    allowed = {"switches.cpp": {"env_flag", "env_choice", "reload_switches"}, "host_stage.cpp": None,
                "comm.cpp": None, "shelfi_internal.h": None}
     for name in sorted(os.listdir(csrc)):
         if not name.endswith((".cpp", ".hip", ".h")):
