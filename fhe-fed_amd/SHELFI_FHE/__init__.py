@@ -188,11 +188,22 @@ class CKKS(Scheme):
         """Decode range (round 6).  Off (default): decrypt reads the shortest tower prefix above
         2^130 and is exact for centred values in [-2^127, 2^127); anything outside that range is
         detected and the call is redone over every tower through the exact multi-word CRT, up to
-        (Q-1)/2 as PALISADE's BigInteger decode (ckks.cpp:189).  The prefix cannot see a value of
-        |X| >= Q'/2 whose residue mod Q' falls inside that range (2^15 / L4: |X| >= 2^163).  On:
-        every decrypt reads every tower through the exact CRT (the same bits wherever both are
-        defined, ~25% slower at 2^15 / L4)."""
+        (Q-1)/2 as PALISADE's BigInteger decode (ckks.cpp:189).  A chain at or below 2^130
+        (multDepth=1, or one or two towers at a lower level) is decoded whole, and a coefficient
+        within Q 2^-16 of +-Q/2 also sends the call to the exact pass, so such chains are exact up
+        to (Q-1)/2 as well.  On longer chains the prefix cannot see a value of |X| >= Q'/2 whose
+        residue mod Q' falls inside [-2^127, 2^127) (2^15 / L4: |X| >= 2^163).  On: every decrypt
+        reads every tower through the exact CRT (the same bits wherever both are defined, ~25%
+        slower at 2^15 / L4)."""
         check(self._lib.shelfi_set_decode_exact(self._ctx, 1 if exact else 0), "set_decode_exact")
+
+    def decode_redo_count(self) -> int:
+        """Decrypt calls of this context (bytes and device API) whose fast pass met a coefficient
+        outside its range and were redone through the exact CRT (shelfi_decode_redo_count).  Calls
+        under set_decode_exact(True) do not count."""
+        n = C.c_uint64()
+        check(self._lib.shelfi_decode_redo_count(self._ctx, C.byref(n)), "decode_redo_count")
+        return int(n.value)
 
     def last_log_precision(self):
         """PALISADE Plaintext::GetLogPrecision of the last flooded decrypt (worst

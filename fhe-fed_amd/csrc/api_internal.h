@@ -147,8 +147,11 @@ DecodePass decode_pass(shelfi_ctx* ctx, uint32_t towers, bool exact);
 
 // The passes of a decrypt call: run(exact) enqueues one pass over the whole call, wait() returns once
 // that pass has completed.  The fast pass first; when it met a coefficient outside the fast CRT's
-// range (GenFlag word 2), the call again, exactly.  Then the flooding's precision verdict; the
-// flooding key is wiped however the call ends.
+// range (GenFlag word 2), the call again, exactly (counted in ctx->decode_redo_count; the caller holds
+// ctx->mu).  Then the flooding's precision verdict; the flooding key is wiped however the call ends.
+// The fast pass of a redone call flooded wrapped values and may have raised the precision word at the
+// call's generation, which the exact pass cannot lower: the redo's flooding reports under a generation
+// of its own, so the verdict is the exact pass's alone (same key and counters: the same noise stream).
 template <class Run, class Wait>
 void decrypt_passes(shelfi_ctx* ctx, const GenFlag& fl, DecodeNoise& dn, Run run, Wait wait) {
   KeyWiper wipe(dn.key);
@@ -157,7 +160,11 @@ void decrypt_passes(shelfi_ctx* ctx, const GenFlag& fl, DecodeNoise& dn, Run run
   } else {
     run(false);
     wait();
-    if (gen_flag_raised(ctx, fl, 2)) run(true);
+    if (gen_flag_raised(ctx, fl, 2)) {
+      ++ctx->decode_redo_count;
+      if (dn.enabled) dn.fail = next_gen_flag(ctx);
+      run(true);
+    }
   }
   wait();
   decode_noise_end(ctx, dn);

@@ -96,7 +96,12 @@ void decode_noise_end(shelfi_ctx* ctx, const DecodeNoise& dn) {
 // boundary, so the towers past the prefix change no output bit.  A coefficient
 // outside that range sets the CRT range flag and the call is redone over every tower through
 // crt_exact_kernel (round 6), as PALISADE's BigInteger decode, up to (Q - 1) / 2.  2^15 / L4
-// (60 + 3 x 52 bits): 3 of 4 towers.  SHELFI_DEC_ALL_TOWERS=1 decodes with every tower (A/B probe
+// (60 + 3 x 52 bits): 3 of 4 towers.  A chain at or below 2^130 (multDepth = 1: 60 + 52 bits; one or
+// two towers at a lower level) is returned whole.  Neither bound above holds there: |X| reaches Q/2,
+// where k's estimate sits on its rounding boundary, and a k that is off by one leaves X -+ Q inside
+// the 128-bit range.  The tables of such a tower set carry DeviceTables::crt_edge, and the launch takes
+// crt_value's EDGE variant, which also flags the band of Q 2^-16 below Q/2 (build_ntt_tables measures
+// the towers as this function does).  SHELFI_DEC_ALL_TOWERS=1 decodes with every tower (A/B probe
 // switch; on chains too wide for crt_value's columns that is crt_exact_kernel).
 static uint32_t decode_towers(const Params& p, uint32_t towers) {
   if (switches().dec_all_towers) return towers;
@@ -130,6 +135,13 @@ int shelfi_set_decode_exact(shelfi_ctx* ctx, int exact) {
   if (!ctx) return SHELFI_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   ctx->decode_exact = exact ? 1 : 0;
+  return SHELFI_OK;
+}
+
+int shelfi_decode_redo_count(shelfi_ctx* ctx, uint64_t* count) {
+  if (!ctx || !count) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  *count = ctx->decode_redo_count;
   return SHELFI_OK;
 }
 

@@ -118,6 +118,7 @@ static std::vector<uint64_t> mw30_neg(std::vector<uint64_t> a, uint32_t n) {
 void free_ntt_tables(DeviceTables& dt) {
   dfree_t(dt.crt_mw);
   dt.crt_nc = 0;
+  dt.crt_edge = false;
   dfree_t(dt.tc);
   dfree_t(dt.psi_rev);
   dfree_t(dt.psi_rev_sh);
@@ -245,6 +246,36 @@ void build_ntt_tables(const Params& p, DeviceTables& dt) {
       mw[4 + (size_t)(L + 1) * NL + j] = (uint32_t)((Qm[j] >> 1) | (j + 1 < NL ? (Qm[j + 1] & 1) << 29 : 0));
     }
     dt.crt_mw = upload(mw.data(), mw.size());
+    // A chain at or below 2^130 (decode_towers' measure) is decoded whole by the fast path: the
+    // launch flags |X'| >= (Q - 1) / 2 - floor(Q 2^-16) as well (TowerConst::crt_edge).  Such a Q is
+    // below 2^(130 + L), three 64-bit words.
+    uint32_t fbits = 0;
+    for (uint32_t t = 0; t < L; ++t) fbits += 63 - (uint32_t)__builtin_clzll(p.q[t]);
+    dt.crt_edge = dt.crt_nc != 0 && fbits <= 130;
+    if (dt.crt_edge) {
+      uint64_t Qw[3] = {0, 0, 0};
+      for (uint32_t j = 0; j < NL && 30 * j < 192; ++j) {
+        Qw[30 * j / 64] |= Qm[j] << (30 * j % 64);
+        if (30 * j % 64 > 34 && 30 * j / 64 + 1 < 3) Qw[30 * j / 64 + 1] |= Qm[j] >> (64 - 30 * j % 64);
+      }
+      const auto shr = [&](uint32_t s, uint64_t* o) {  // o = Q >> s, 0 < s < 64
+        for (int w = 0; w < 3; ++w) o[w] = (Qw[w] >> s) | (w + 1 < 3 ? Qw[w + 1] << (64 - s) : 0);
+      };
+      uint64_t h[3], m[3], e[3];
+      shr(1, h);
+      shr(16, m);
+      uint64_t borrow = 0;
+      for (int w = 0; w < 3; ++w) {
+        const u128 d = (u128)h[w] - m[w] - borrow;
+        e[w] = (uint64_t)d;
+        borrow = (uint64_t)(d >> 64) & 1;
+      }
+      const bool past = e[2] != 0 || (e[1] >> 63) != 0;  // 2^127 or more: the 128-bit range test covers it
+      for (uint32_t t = 0; t < L; ++t) {
+        tc[t].crt_edge[0] = past ? ~0ull : e[0];
+        tc[t].crt_edge[1] = past ? ~0ull : e[1];
+      }
+    }
   }
   dt.tc = upload(tc.data(), L);
   dt.red_ok = true;

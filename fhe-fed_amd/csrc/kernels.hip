@@ -2087,7 +2087,17 @@ void launch_encrypt_approx(const Params& p, const DeviceTables& dt, const Device
 // (Q > 2^130), |X| < 2^127 puts sum_t y_t / q_t within 2^-3 of k, and the binary32 estimate errs by
 // at most ~L 2^-21 (terms (y_t >> s_t) * (2^s_t / q_t), y_t >> s_t < 2^32, TowerConst::crt_sh), so
 // k is exact and the output bits are the round-5 ones.
-template <int NC, class YF>
+//
+// EDGE (DeviceTables::crt_edge): a chain at or below 2^130 is decoded whole, and there that argument
+// fails near +-Q/2: sum_t y_t / q_t = k + X / Q lies within the estimate's error of the rounding
+// boundary k +- 1/2, a k that is off by one gives X' = X -+ Q, and with Q/2 < 2^127 that wrong X' is
+// inside the 128-bit range.  The estimate errs by less than 2^-18 for L <= 7 (each term's three
+// binary32 roundings, 3 x 2^-24 of a term below 1; each running sum's, half an ulp of a value below
+// 8, 2^-22; the + 0.5's), so k can be wrong only when |X| > Q/2 - Q 2^-18, and then |X'| >= Q/2 as
+// well.  Flagging every |X'| >= (Q - 1) / 2 - floor(Q 2^-16) (TowerConst::crt_edge, 4x that bound)
+// therefore catches every wrong output; the right ones in that band are merely redone exactly.  Not
+// instantiated for prefixes above 2^130, whose code is unchanged.
+template <int NC, bool EDGE = false, class YF>
 __device__ __forceinline__ double crt_value(YF yf, uint32_t L, const TowerConst* __restrict__ tcs,
                                             double inv_scale, bool& wide) {
   static_assert(NC >= 5 && NC <= 7, "crt columns");
@@ -2126,7 +2136,11 @@ __device__ __forceinline__ double crt_value(YF yf, uint32_t L, const TowerConst*
     xlo = ~xlo + 1;
     xhi = ~xhi + (xlo == 0 ? 1 : 0);
   }
-  double v = __dadd_rn(__dmul_rn((double)xhi, 18446744073709551616.0), (double)xlo);
+  if constexpr (EDGE) {  // |X'| >= (Q - 1) / 2 - floor(Q 2^-16): k may be off by one
+    const uint64_t elo = tcs[0].crt_edge[0], ehi = tcs[0].crt_edge[1];
+    wide |= xhi > ehi || (xhi == ehi && xlo >= elo);
+  }
+  double v =__dadd_rn(__dmul_rn((double)xhi, 18446744073709551616.0), (double)xlo);
   if (neg) v = -v;
   return __dmul_rn(v, inv_scale);
 }
@@ -2240,7 +2254,7 @@ __device__ __forceinline__ double crt_exact_value(YF yf, uint32_t L, const Tower
 // (crt_value: NC exact columns, *wide set when X is outside the 128-bit range); then (double)X *
 // (1/scale) (PALISADE Decode: ConvertToDouble * scalingFactorPre * 2^-p).  Written at bitrev(i) for
 // FFTSpecial.  EXACT: crt_exact_kernel's arithmetic (crt_exact_value, every |X| <= (Q - 1) / 2).
-template <int NC, bool EXACT = false>
+template <int NC, bool EXACT = false, bool EDGE = false>
 __global__ __launch_bounds__(256) void crt_decode_kernel(const uint64_t* __restrict__ dbuf,
                                                          uint64_t K, uint32_t logN, uint32_t logS,
                                                          uint32_t L,
@@ -2280,7 +2294,7 @@ __global__ __launch_bounds__(256) void crt_decode_kernel(const uint64_t* __restr
     if constexpr (EXACT)
       res[part] = crt_exact_value(yf, L, tcs, mw, inv_scale);
     else
-      res[part] = crt_value<NC>(yf, L, tcs, inv_scale, wide);
+      res[part] = crt_value<NC, EDGE>(yf, L, tcs, inv_scale, wide);
   }
   if (wide) gen_flag_set(wide_flag, 2);
   if (!tiled) {
@@ -2309,7 +2323,7 @@ __global__ __launch_bounds__(256) void crt_decode_kernel(const uint64_t* __restr
 // at 2^15 / L4, 5 workgroups per CU; the round-4 rows padded to 68 u64 ran the same, 0.960 vs 0.959
 // us per decrypted ciphertext, profiles/r05d).
 constexpr size_t kCrtFuseLds = 48 << 10;
-template <int LOGR, int NC>
+template <int LOGR, int NC, bool EDGE = false>
 __global__ __launch_bounds__(256) void ntt_inv_cols_crt(const uint64_t* __restrict__ dbuf, uint32_t L,
                                                         uint32_t logN, uint32_t logS,
                                                         const uint64_t* __restrict__ tw,
@@ -2377,7 +2391,8 @@ __global__ __launch_bounds__(256) void ntt_inv_cols_crt(const uint64_t* __restri
 #pragma unroll
     for (int part = 0; part < 2; ++part) {
       const uint32_t rr = r + part * (R / 2);
-      res[part] = crt_value<NC>([&](uint32_t t) { return ys[t][rr][ucol(rr, u)]; }, L, tcs, inv_scale, wide);
+      res[part] =
+          crt_value<NC, EDGE>([&](uint32_t t) { return ys[t][rr][ucol(rr, u)]; }, L, tcs, inv_scale, wide);
     }
     const uint32_t i = (col + BLK * r) >> gapLog;
     fbuf[k * S + bitrev_dev(i, logS)] = make_double2(res[0], res[1]);
@@ -2945,6 +2960,9 @@ void launch_decrypt(const Params& p, const DeviceTables& dt, const DeviceKeys& d
   exact = exact || dt.crt_nc == 0;  // towers too wide for crt_value's columns: always exact
   if (exact && !dt.crt_mw) throw Error{SHELFI_ERR_STATE, "decrypt: no exact CRT table for these towers"};
   if (!exact && !crt_flag.p) throw Error{SHELFI_ERR_STATE, "decrypt: the fast CRT needs a range flag"};
+  // a chain at or below 2^130, decoded whole: the kernels' EDGE variants (crt_value), 5 columns
+  const bool edge = !exact && dt.crt_edge;
+  if (edge && dt.crt_nc != 5) throw Error{SHELFI_ERR_STATE, "decrypt: a short chain needs 5 CRT columns"};
   const uint32_t logS = __builtin_ctz(p.batch);
   uint64_t* dbuf = reinterpret_cast<uint64_t*>(scratch);
   double2* fbuf = reinterpret_cast<double2*>(dbuf + K * (uint64_t)p.L * p.N);
@@ -2993,13 +3011,14 @@ void launch_decrypt(const Params& p, const DeviceTables& dt, const DeviceKeys& d
                          logR == 0 ? 1 : 0, ct, dk.sk, dk.sk_sh, sum_in ? 1 : 0, ct_L);
     if (logR > 0 && fuse) {
       const uint64_t nbf = K * ((p.N >> logR) / 64);
-#define CRT_FUSED(LR, NCC)                                                                                    \
-  hipLaunchKernelGGL((ntt_inv_cols_crt<LR, NCC>), dim3((uint32_t)nbf), dim3(256), fuse_lds, s, dbuf, p.L, p.logN, \
-                     logS, dt.ipsi_rev, dt.ipsi_rev_sh, dt.tc, 1.0 / scale, fbuf, crt_flag)
+#define CRT_FUSED(LR, NCC, EDGE)                                                                              \
+  hipLaunchKernelGGL((ntt_inv_cols_crt<LR, NCC, EDGE>), dim3((uint32_t)nbf), dim3(256), fuse_lds, s, dbuf, p.L, \
+                     p.logN, logS, dt.ipsi_rev, dt.ipsi_rev_sh, dt.tc, 1.0 / scale, fbuf, crt_flag)
 #define CRT_FUSED_NC(LR)                                  \
-  if (dt.crt_nc == 5) CRT_FUSED(LR, 5);                   \
-  else if (dt.crt_nc == 6) CRT_FUSED(LR, 6);              \
-  else CRT_FUSED(LR, 7);
+  if (edge) CRT_FUSED(LR, 5, true);                       \
+  else if (dt.crt_nc == 5) CRT_FUSED(LR, 5, false);       \
+  else if (dt.crt_nc == 6) CRT_FUSED(LR, 6, false);       \
+  else CRT_FUSED(LR, 7, false);
       switch (logR) {
         case 1: CRT_FUSED_NC(1) break;
         case 2: CRT_FUSED_NC(2) break;
@@ -3021,6 +3040,9 @@ void launch_decrypt(const Params& p, const DeviceTables& dt, const DeviceKeys& d
     const dim3 cg((uint32_t)((slots + 255) / 256));
     if (exact)
       hipLaunchKernelGGL((crt_decode_kernel<5, true>), cg, dim3(256), 0, s, dbuf, K, p.logN, logS, p.L, dt.tc,
+                         dt.crt_mw, 1.0 / scale, fbuf, crt_flag);
+    else if (edge)
+      hipLaunchKernelGGL((crt_decode_kernel<5, false, true>), cg, dim3(256), 0, s, dbuf, K, p.logN, logS, p.L, dt.tc,
                          dt.crt_mw, 1.0 / scale, fbuf, crt_flag);
     else if (dt.crt_nc == 5)
       hipLaunchKernelGGL((crt_decode_kernel<5>), cg, dim3(256), 0, s, dbuf, K, p.logN, logS, p.L, dt.tc,

@@ -140,6 +140,10 @@ struct TowerConst {
   // the CRT in 30-bit limbs (crt_value, L <= 7): (Q/q_t) mod 2^210 and (2^210 - Q) mod 2^210
   // (the same in every tower), limbs 0..6 of 30 bits; a launch uses the first DeviceTables::crt_nc
   uint32_t crt30[7], nq30[7];
+  // crt_value<NC, true> (DeviceTables::crt_edge, chains at or below 2^130): the fast CRT also flags
+  // |X'| >= crt_edge = (Q - 1) / 2 - floor(Q 2^-16) as {low, high} 64-bit words (the same in every
+  // tower; all ones when that is 2^127 or more: the 128-bit range test then covers it)
+  uint64_t crt_edge[2];
 };
 
 constexpr int kEncVTab = 4 * 81, kEncETab = 128, kEncTab = kEncVTab + kEncETab;
@@ -173,8 +177,12 @@ struct DeviceTables {
   // exactly (ceil((bits(Q) + bits(L) + 1) / 30), at least 5), or 0 when that exceeds 7 or L > 7: such
   // tower sets always decode through crt_exact_kernel.  crt_mw: that kernel's table (uint32 words):
   // [0] NL limbs, [1] NW 64-bit words of |X|, [2..3] 0, then (Q/q_t) [L][NL], 2^(30 NL) - Q [NL],
-  // (Q - 1) / 2 [NL], all in 30-bit limbs.
+  // (Q - 1) / 2 [NL], all in 30-bit limbs.  crt_edge: the towers' bit count (sum of floor(log2 q_t),
+  // decode_towers' measure) is at most 130 -- a chain the fast path decodes whole, where a binary32
+  // k that is off by one near +-Q/2 lands inside the 128-bit range: the launch takes the kernels'
+  // EDGE variants (TowerConst::crt_edge; crt_nc is 5 on every such chain).
   uint32_t crt_nc = 0;
+  bool crt_edge = false;
   uint32_t* crt_mw = nullptr;
 };
 constexpr int kCrtMwMaxLimbs = 36;  // crt_exact_kernel: 16 towers below 2^60, times L, plus sign
@@ -257,6 +265,7 @@ struct shelfi_ctx {
   int decode_noise = 1;          // shelfi_set_decode_noise (PALISADE floods every decode)
   double decode_m_factor = 1.0;
   int decode_exact = 0;          // shelfi_set_decode_exact: every decrypt over every tower, exact CRT
+  uint64_t decode_redo_count = 0;  // decrypt calls whose fast pass was redone exactly (shelfi_decode_redo_count)
   int last_log_error = -1;       // of the last flooded decrypt, -1 if none
   bool log_error_pending = false;  // dev_flag[2] holds a newer one, read on demand (shelfi_decode_log_error)
   std::string pal_ctx_obj;       // PALISADE keys: embedded context object (§8 f1)

@@ -130,11 +130,19 @@ int shelfi_set_decode_noise(shelfi_ctx* ctx, int enabled, double m_factor);
  * modulus Q' exceeds 2^130 and reconstructs each coefficient exactly while its centred value is in
  * [-2^127, 2^127); a coefficient outside that range is detected and the call is redone over every
  * tower through an exact multi-word CRT, up to (Q - 1) / 2 (PALISADE's BigInteger decode,
- * ckks.cpp:189).  The prefix cannot see a value of |X| >= Q'/2 whose residue mod Q' falls inside
- * [-2^127, 2^127) (|X| >= 2^163 at 2^15 / L4).  exact = 1: every decrypt reads every tower and
+ * ckks.cpp:189).  A chain at or below 2^130 (multDepth = 1, or a ciphertext of one or two towers at
+ * a lower level) is decoded whole: there the fast pass is sure of a coefficient only while
+ * |X| < Q/2 - Q 2^-16, and any coefficient nearer to +-Q/2 sends the call to the exact pass, so
+ * decrypt is exact up to (Q - 1) / 2 on such chains too.  On longer chains the prefix cannot see a
+ * value of |X| >= Q'/2 whose residue mod Q' falls inside [-2^127, 2^127) (|X| >= 2^163 at
+ * 2^15 / L4): that alone is wrong by default.  exact = 1: every decrypt reads every tower and
  * decodes through the exact CRT (same output bits wherever both are defined; ~25% slower at
  * 2^15 / L4).  Applies to shelfi_decrypt and the shelfi_dev_decrypt* calls. */
 int shelfi_set_decode_exact(shelfi_ctx* ctx, int exact);
+/* Decrypt calls of this context (shelfi_decrypt, shelfi_dev_decrypt*) whose fast pass met a
+ * coefficient outside its range and were redone through the exact CRT.  Calls made under
+ * shelfi_set_decode_exact(ctx, 1) have no fast pass and do not count. */
+int shelfi_decode_redo_count(shelfi_ctx* ctx, uint64_t* count);
 /* logError of the last flooded decrypt (max over its ciphertexts; PALISADE
  * Plaintext::GetLogError), -1 if none.  Precision = scale_bits - logError. */
 int shelfi_decode_log_error(shelfi_ctx* ctx, int* log_error);

@@ -11,7 +11,13 @@ all-tower centred CRT returns.
 Round 6: the kernel's columns hold X' = sum_t y_t (Q'/q_t) - k Q' exactly (NC 30-bit columns,
 DeviceTables::crt_nc) and flag every X' outside (-2^127, 2^127); a flagged call is redone over every
 tower through crt_exact_kernel (any |X| <= (Q-1)/2, the oracle's multi-word centring and Horner
-conversion, `or_crt_centered_double`)."""
+conversion, `or_crt_centered_double`).
+
+A chain at or below 2^130 (multDepth = 1: 60 + 52 bits; one or two towers at a lower level) is decoded
+whole, and there a binary32 k that is off by one near +-Q/2 gives X' = X -+ Q inside (-2^127, 2^127):
+nothing above flags it.  On such chains the kernel (crt_value<NC, EDGE>, TowerConst::crt_edge) also flags
+every |X'| >= (Q-1)/2 - floor(Q 2^-16); `_crt_edge` and `_kernel_crt_flag` restate that rule, and
+test_short_chain_edge_is_right_or_flagged holds it to "equal to X, or flagged" at the edge."""
 import numpy as np
 import pytest
 
@@ -35,8 +41,22 @@ def _crt_nc(q):
     return nc if (len(q) <= 7 and nc <= 7) else 0
 
 
-def _kernel_crt_flag(res, q):
-    """crt_value with its range test: (X mod 2^128 as signed, flagged)."""
+def _crt_edge(q):
+    """context.cpp build_ntt_tables, TowerConst::crt_edge: on a chain at or below 2^130 (decode_towers'
+    bit count) the fast CRT also flags |X'| >= (Q-1)/2 - floor(Q 2^-16); None where the kernel has no
+    such test (longer chains) or it cannot fire (2^127 or more: the 128-bit range test covers it)."""
+    if sum(int(v).bit_length() - 1 for v in q) > 130:
+        return None
+    Q = 1
+    for qt in q:
+        Q *= int(qt)
+    e = (Q >> 1) - (Q >> 16)
+    return None if e >> 127 else e
+
+
+def _kernel_crt_flag(res, q, edge=True):
+    """crt_value with its range tests: (X mod 2^128 as signed, flagged).  edge=False: without the
+    short-chain test (the kernel before it had one)."""
     NC = _crt_nc(q)
     assert NC
     Q = 1
@@ -60,6 +80,9 @@ def _kernel_crt_flag(res, q):
     x128 = x128 - (1 << 128) if x128 >> 127 else x128
     hi = Xp >> 127  # bits 127 .. W-1 must all equal the sign
     flagged = hi not in (0, (1 << (W - 127)) - 1)
+    e = _crt_edge(q) if edge else None
+    if e is not None:
+        flagged = flagged or abs(x128) >= e
     return x128, flagged
 
 
@@ -141,13 +164,23 @@ def test_fast_crt_flags_exactly_the_values_outside_its_range(N, L):
     small = [int(v) for v in rng.integers(-(1 << 62), 1 << 62, 32)]
     small += [(1 << 127) - 1, -(1 << 127) + 1, 0, 1, -1]
     small += [(int(rng.integers(1, 1 << 62)) << int(rng.integers(0, 64))) * s for s in (1, -1) for _ in range(16)]
+    edge = _crt_edge(qp)  # a chain decoded whole: sure of X only below (Q-1)/2 - floor(Q 2^-16)
     for X in small:
-        if abs(X) >= min(1 << 127, (Qall - 1) // 2):
+        if abs(X) >= min(1 << 127, (Qall - 1) // 2) or (edge is not None and abs(X) >= edge):
             continue
         x128, flagged = _kernel_crt_flag([X % qt for qt in qp], qp)
         assert not flagged and x128 == X, X
     if Qp // 2 <= 1 << 127:
-        return  # the prefix is the whole chain below 2^128: nothing lies outside the fast range
+        # the prefix is the whole chain below 2^128: what lies outside the fast range is the band at
+        # +-Q/2 (test_short_chain_edge_is_right_or_flagged); the rest of the range stays unflagged
+        assert edge is not None and Lp == L
+        for X in (edge - 1, -(edge - 1), Qall // 4, -(Qall // 4)):
+            x128, flagged = _kernel_crt_flag([X % qt for qt in qp], qp)
+            assert not flagged and x128 == X, X
+        for X in (edge, -edge, (Qall - 1) // 2, -((Qall - 1) // 2)):
+            _, flagged = _kernel_crt_flag([X % qt for qt in qp], qp)
+            assert flagged, X
+        return
     x128, flagged = _kernel_crt_flag([-(1 << 127) % qt for qt in qp], qp)
     assert not flagged and x128 == -(1 << 127)  # the signed 128-bit range is [-2^127, 2^127)
     wide = [(1 << 127), -(1 << 127) - 1, (1 << 127) + 5, (Qp - 1) // 2, -((Qp - 1) // 2)]
@@ -165,6 +198,51 @@ def test_fast_crt_flags_exactly_the_values_outside_its_range(N, L):
         r = r - Qp if r > Qp // 2 else r
         _, flagged = _kernel_crt_flag([X % qt for qt in qp], qp)
         assert flagged == (not -(1 << 127) <= r < 1 << 127), X
+
+
+def _short_chain(name):
+    if name == "2^13/L2":  # multDepth = 1, the reference's fixed setting: 60 + 52 bits
+        return [int(v) for v in O.params_generate(1 << 13, 2)[0]]
+    q = [int(v) for v in O.params_generate(1 << 15, 4)[0]]
+    return q[:1] if name == "one tower" else q[:2]  # what a ciphertext holds at a lower level
+
+
+@pytest.mark.parametrize("chain", ["2^13/L2", "one tower", "2^15/L4 first two"])
+def test_short_chain_edge_is_right_or_flagged(chain):
+    """Chains decode_towers returns whole because they are at or below 2^130.  For 2 x 2051 values
+    X = +-((Q-1)/2 - d), d uniform in [0, Q 2^-19) and d in {0, 1, 2}, the kernel's value is X or the
+    coefficient is flagged (the call is then redone exactly).  Without the short-chain test some of
+    them are wrong by Q and unflagged (what the kernel did before); every such value lies within
+    Q 2^-18 of the edge, the bound on the binary32 k's error that the 2^-16 margin is taken from; and
+    ordinary values |X| < Q/4 are right and unflagged, so an ordinary call stays on the fast path."""
+    q = _short_chain(chain)
+    assert _decode_towers(q) == len(q) and _crt_nc(q) == 5
+    Q = 1
+    for qt in q:
+        Q *= qt
+    assert Q < 1 << 127
+    half = (Q - 1) // 2
+    edge = _crt_edge(q)
+    assert edge == half - (Q >> 16)
+    rng = np.random.default_rng(len(chain))
+    ds = [0, 1, 2] + [int.from_bytes(rng.bytes(16), "little") % (Q >> 19) for _ in range(2048)]
+    wrong_before = 0
+    for d in ds:
+        for X in (half - d, -(half - d)):
+            res = [X % qt for qt in q]
+            assert O.crt_centered(res, q) == X  # the oracle's centring reaches (Q-1)/2
+            x128, flagged = _kernel_crt_flag(res, q)
+            assert flagged or x128 == X, (X, x128)
+            x0, f0 = _kernel_crt_flag(res, q, edge=False)
+            if x0 != X:
+                assert not f0 and abs(x0 - X) == Q  # k off by one, inside the 128-bit range
+                assert half - abs(X) < Q >> 18
+                wrong_before += 1
+    assert wrong_before > 0  # these inputs do reach the failure
+    for _ in range(512):
+        X = int.from_bytes(rng.bytes(16), "little") % (Q // 4) * int(rng.choice([-1, 1]))
+        x128, flagged = _kernel_crt_flag([X % qt for qt in q], q)
+        assert not flagged and x128 == X, X
 
 
 @pytest.mark.parametrize("N,L", [(1 << 15, 4), (1 << 16, 6), (1 << 13, 2), (1 << 17, 16)])
