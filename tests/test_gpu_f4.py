@@ -3,7 +3,8 @@ relinearization, ModReduce and decrypt at a level — every residue bit-exact ag
 oracle's restatement (oracle/ckks_oracle.c or_evk_keygen / or_eval_mult / or_rescale),
 and the decrypted values equal to the plaintext products.  PALISADE parity of the key
 switching itself is unpinned (tests/test_oracle_f4.py says why); its parameters (dnum,
-special primes, roots) are pinned by the reference's key-eval-mult.txt."""
+special primes, roots) are pinned by the reference's key-eval-mult.txt.  Every level, digits of
+3 and 4 towers and the operand edges are in tests/test_gpu_f4_levels.py."""
 import os
 
 import numpy as np
