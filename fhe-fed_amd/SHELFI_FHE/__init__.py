@@ -255,6 +255,53 @@ class CKKS(Scheme):
                                         sk.ctypes.data_as(_lib.u64p)))
         return pk, sk
 
+    # ------------------------------- threshold CKKS (mkhe.cpp RunCKKS) --
+    def multipartyKeyGen(self, prev_public: np.ndarray) -> None:
+        """cc->MultipartyKeyGen(prev.publicKey) (mkhe.cpp:282): one step of the threshold key chain.
+        Keeps a = prev.a, samples this party's s_i and e_i and installs
+        (pk = (prev.b + NTT(e_i) - a NTT(s_i), a), sk = NTT(s_i)) in memory.  The lead party calls
+        genCryptoContextAndKeyGen() with cryptodir ""; after the chain every party calls
+        set_keys(pk_joint, own sk)."""
+        pk = np.ascontiguousarray(prev_public, dtype=np.uint64)
+        inf = self.info()
+        if pk.size != 2 * inf["num_towers"] * inf["ring_dim"]:
+            raise ValueError("the previous public key must be [2][L][N]")
+        check(self._lib.shelfi_multiparty_keygen(self._ctx, pk.ctypes.data_as(_lib.u64p)), "multipartyKeyGen")
+        self._apply_wire()
+
+    def set_threshold_noise(self, sigma: float = 2.0 ** 20) -> None:
+        """Standard deviation of the smudging noise each partial decryption adds (default 2^20);
+        0 = no noise, deterministic partials (parity mode)."""
+        check(self._lib.shelfi_set_threshold_noise(self._ctx, float(sigma)), "set_threshold_noise")
+
+    def partialDecrypt(self, data, lead: bool) -> bytes:
+        """cc->MultipartyDecryptLead / MultipartyDecryptMain (mkhe.cpp:395-400) of ciphertext bytes in any
+        wire format with this context's key share -> a partial-decryption blob ("SHPD")."""
+        if isinstance(data, str):
+            data = data.encode("latin-1")
+        b = bytes(data)
+        out = _lib.u8p()
+        n = C.c_size_t()
+        check(self._lib.shelfi_partial_decrypt(self._ctx, C.cast(C.c_char_p(b), _lib.u8p), len(b), 1 if lead else 0,
+                                               C.byref(out), C.byref(n)), "partialDecrypt")
+        return self._take(out, n.value)
+
+    def fuseDecrypt(self, partials, data_dimensions: int) -> np.ndarray:
+        """cc->MultipartyDecryptFusion (mkhe.cpp:402): every party's partial-decryption blob (exactly one
+        of them the lead's) -> float64[data_dimensions].  Needs no keys."""
+        blobs = _as_bytes_list(list(partials))
+        P = len(blobs)
+        arr = (_lib.u8p * P)()
+        lens = (C.c_size_t * P)()
+        for i, b in enumerate(blobs):
+            arr[i] = C.cast(C.c_char_p(b), _lib.u8p)
+            lens[i] = len(b)
+        n = int(data_dimensions)
+        out = np.empty(n, np.float64)
+        check(self._lib.shelfi_fuse_decrypt(self._ctx, arr, lens, P, n, out.ctypes.data_as(_lib.f64p)),
+              "fuseDecrypt")
+        return out
+
     # ------------------------------------- f4: EvalMult / ModReduce (§8 f4) --
     def evalMultKeyGen(self) -> None:
         """cc->EvalMultKeyGen(sk): the HYBRID relinearization key (s^2 -> s), generated on
@@ -408,6 +455,34 @@ def blob_info(blob: bytes) -> dict:
     return {"num_cts": int(k.value), "depth": int(d.value), "scale": float(s.value),
             "key_id": int(kid.value),
             "format": "packed" if int.from_bytes(bytes(blob[4:6]), "little") == 2 else "shelfi"}
+
+
+def partial_blob_info(blob: bytes) -> dict:
+    """Host-only: the header of a partial-decryption blob (CKKS.partialDecrypt)."""
+    lib = _lib.load()
+    k, t, ld, sc, kid = C.c_uint64(), C.c_uint32(), C.c_int(), C.c_double(), C.c_uint64()
+    check(lib.shelfi_partial_blob_info(C.cast(C.c_char_p(blob), _lib.u8p), len(blob), C.byref(k), C.byref(t),
+                                       C.byref(ld), C.byref(sc), C.byref(kid)), "partial_blob_info")
+    return {"num_cts": int(k.value), "towers": int(t.value), "lead": bool(ld.value), "scale": float(sc.value),
+            "key_id": int(kid.value)}
+
+
+def partial_blob_pack(residues: np.ndarray, lead: bool, scale: float, params_id: int, key_id: int, batch: int,
+                      depth: int = 1) -> bytes:
+    """Host-only: a partial-decryption blob from host residues [K][L][N] and its metadata."""
+    lib = _lib.load()
+    r = np.ascontiguousarray(residues, dtype=np.uint64)
+    if r.ndim != 3:
+        raise ValueError("partial residues must be [K][L][N]")
+    out = _lib.u8p()
+    n = C.c_size_t()
+    check(lib.shelfi_partial_blob_pack(r.shape[2], r.shape[1], int(batch), r.shape[0], int(depth), float(scale),
+                                       int(params_id), int(key_id), 1 if lead else 0,
+                                       r.ctypes.data_as(_lib.u64p), C.byref(out), C.byref(n)), "partial_blob_pack")
+    try:
+        return C.string_at(out, n.value)
+    finally:
+        lib.shelfi_free(out)
 
 
 def blob_pack(ckks: "CKKS", residues: np.ndarray, depth: int = 1, scale: float | None = None) -> bytes:

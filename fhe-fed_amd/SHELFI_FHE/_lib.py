@@ -179,6 +179,22 @@ SIGNATURES = {
     "shelfi_palisade_evalkey_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, u64p]),
     "shelfi_palisade_evalkey_rewrite": (C.c_int, [C.c_char_p, C.c_size_t, u64p, C.POINTER(u8p),
                                                   C.POINTER(C.c_size_t)]),
+    # threshold CKKS (mkhe.cpp RunCKKS): key chain, partial decryption, fusion (threshold.hip)
+    "shelfi_multiparty_keygen": (C.c_int, [C.c_void_p, u64p]),
+    "shelfi_set_threshold_noise": (C.c_int, [C.c_void_p, C.c_double]),
+    "shelfi_dev_partial_decrypt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p,
+                                             C.c_void_p]),
+    "shelfi_dev_fuse_decrypt": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, C.c_uint32,
+                                          C.c_double, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "shelfi_partial_decrypt": (C.c_int, [C.c_void_p, u8p, C.c_size_t, C.c_int, C.POINTER(u8p),
+                                         C.POINTER(C.c_size_t)]),
+    "shelfi_fuse_decrypt": (C.c_int, [C.c_void_p, C.POINTER(u8p), C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t,
+                                      f64p]),
+    "shelfi_partial_blob_info": (C.c_int, [u8p, C.c_size_t, u64p, C.POINTER(C.c_uint32), C.POINTER(C.c_int), f64p,
+                                           u64p]),
+    "shelfi_partial_blob_pack": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_double,
+                                           C.c_uint64, C.c_uint64, C.c_int, u64p, C.POINTER(u8p),
+                                           C.POINTER(C.c_size_t)]),
     "shelfi_fft_twiddles": (C.c_int, [C.c_uint32, f64p, f64p, f64p, f64p]),
     "shelfi_gauss_cdt": (C.c_int, [C.c_double, u64p, C.c_int]),
 }

@@ -416,6 +416,49 @@ def decrypt_sum(ckks, ct, terms: int, n: int, scale: float, out=None):
     return out
 
 
+def partial_decrypt(ckks, ct, lead: bool, out=None):
+    """This party's partial decryption of K ciphertexts (any number of towers <= L) with the context's
+    key share and smudging noise (CKKS.set_threshold_noise): [K][2][l][N] -> [K][l][N], lead: c0 + c1 s
+    + e (MultipartyDecryptLead), else c1 s + e (MultipartyDecryptMain)."""
+    torch = _torch()
+    _check_ct(ct, ckks, any_level=True)
+    K, _, l, N = ct.shape
+    if out is None:
+        out = torch.empty((K, l, N), dtype=ct.dtype, device=ct.device)
+    if (not out.is_cuda or not out.is_contiguous() or out.element_size() != 8 or tuple(out.shape) != (K, l, N)
+            or out.device != ct.device):
+        raise ValueError("out must be a contiguous [K][l][N] 64-bit tensor on ct's device")
+    check(_lib.load().shelfi_dev_partial_decrypt(ckks._ctx, C.c_void_p(ct.data_ptr()), K, int(l), 1 if lead else 0,
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(ct))),
+          "dev_partial_decrypt")
+    return out
+
+
+def fuse_decrypt(ckks, partials: Sequence, n: int, scale: float, out=None):
+    """MultipartyDecryptFusion of 1..16 partial decryptions [K][l][N] (device tensors of one shape on one
+    device) into n float64 values; needs no keys.  The partials are summed while decrypt's first pass
+    loads them; the rest is decrypt()'s chain."""
+    torch = _torch()
+    partials = list(partials)
+    L, N = _ln(ckks)
+    if partials:
+        p0 = partials[0]
+        for p in partials:
+            if (not p.is_cuda or not p.is_contiguous() or p.element_size() != 8 or p.dim() != 3
+                    or p.shape != p0.shape or p.device != p0.device or p.shape[2] != N):
+                raise ValueError("partials must be contiguous 64-bit CUDA tensors of one shape [K][l][N]")
+        K, towers, dev = int(p0.shape[0]), int(p0.shape[1]), p0.device
+    else:
+        K, towers, dev = 0, L, "cuda:%d" % ckks.info()["device"]
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=dev)
+    ptrs = (C.c_void_p * max(1, len(partials)))(*[p.data_ptr() for p in partials])
+    stream = _stream_ptr(partials[0]) if partials else 0
+    check(_lib.load().shelfi_dev_fuse_decrypt(ckks._ctx, ptrs, len(partials), K, towers, float(scale), int(n),
+                                              C.c_void_p(out.data_ptr()), C.c_void_p(stream)), "dev_fuse_decrypt")
+    return out
+
+
 def mult(ckks, a, b, out=None):
     """cc->EvalMult(a, b) for K ciphertext pairs of the same level: tensor product +
     HYBRID relinearization (needs ckks.evalMultKeyGen()).  Scale: scale_a * scale_b."""

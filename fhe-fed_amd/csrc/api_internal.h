@@ -47,6 +47,13 @@ struct BlobHeader {
   uint32_t encoding;       // 4 = CKKSPacked (PALISADE PlaintextEncodings)
 };
 static_assert(sizeof(BlobHeader) == 64, "blob header must be 64 bytes");
+// A partial decryption (threshold scheme) travels under the same 64-byte header with magic "SHPD",
+// version 1 and a payload of K x L x N uint64 residues [ct][tower][coeff]: logN, L, K, depth, scale,
+// params_id, batch and encoding as in the ciphertexts it was made from, key_id the joint public key's.
+// The `level` word (always 0 in a ciphertext blob) carries the role: 1 = lead (c0 + c1 s + e,
+// MultipartyDecryptLead), 0 = main (c1 s + e, MultipartyDecryptMain); any other value is refused.
+BlobHeader parse_partial(const uint8_t* blob, size_t len, const shelfi_ctx* ctx);
+BlobHeader make_partial_header(const shelfi_ctx* ctx, uint64_t K, uint32_t depth, double scale, bool lead);
 
 // Packed wire payload sizes (version-2 blobs): bytes of one (ct, poly) group of the first Lu towers.
 uint64_t packed_poly_bytes(const Params& p, uint32_t Lu);
@@ -169,6 +176,15 @@ void decrypt_passes(shelfi_ctx* ctx, const GenFlag& fl, DecodeNoise& dn, Run run
   wait();
   decode_noise_end(ctx, dn);
 }
+
+// ---------------------------------------------------------- dev_api.cpp ----
+// The device decrypt driver and the threshold partial decryption behind the shelfi_dev_* entry points,
+// for the bytes API as well (the caller holds ctx->mu, has selected the device and checked the keys;
+// both return with `s` synchronised).  fuse: threshold fusion of fuse->P partials, no ct_dev, no keys.
+void dev_decrypt_locked(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, double scale, size_t n,
+                        double* out_dev, hipStream_t s, bool sum_in, const FuseIn* fuse);
+void partial_decrypt_locked(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, bool lead,
+                            uint64_t* out_dev, hipStream_t s);
 
 }  // namespace shelfi
 

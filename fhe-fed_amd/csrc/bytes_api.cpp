@@ -593,4 +593,115 @@ int shelfi_decrypt(shelfi_ctx* ctx, const uint8_t* blob, size_t len, size_t n, d
   });
 }
 
+// mkhe.cpp:395-400: this party's partial decryption of a ciphertext batch (any wire format), as an
+// "SHPD" blob.  The batch is uploaded in chunks, partially decrypted on the device (threshold.hip) and
+// copied out; free with shelfi_free.
+int shelfi_partial_decrypt(shelfi_ctx* ctx, const uint8_t* blob, size_t len, int lead, uint8_t** out,
+                           size_t* out_len) {
+  if (!ctx || !out || !out_len) return SHELFI_ERR_ARG;
+  *out = nullptr;
+  *out_len = 0;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    require_keys(ctx);
+    DeviceGuard g(ctx->device);
+    const Params& p = ctx->p;
+    const CtLayout h = open_cts(ctx, blob, len);
+    const size_t poly_bytes = (size_t)p.L * p.N * 8;
+    const size_t total = sizeof(BlobHeader) + h.K * poly_bytes;
+    struct Free {
+      uint8_t* p;
+      ~Free() { std::free(p); }
+    } res{(uint8_t*)std::malloc(total)};
+    if (!res.p) throw std::bad_alloc();
+    const BlobHeader hd = make_partial_header(ctx, h.K, h.depth, h.scale, lead != 0);
+    std::memcpy(res.p, &hd, sizeof(hd));
+    if (h.K) {
+      const uint64_t kc = std::min<uint64_t>(h.K, std::max<uint64_t>(1, (64ull << 20) / (2 * poly_bytes)));
+      const uint64_t pct = 2 * packed_poly_bytes(p, p.L);
+      const size_t cin = kc * 2 * poly_bytes, pout = kc * poly_bytes, pin = h.packed ? kc * pct : 0;
+      uint8_t* io = (uint8_t*)ensure(ctx->io, ctx->io_bytes, cin + pout + pin);
+      uint8_t *cb = io, *ob = io + cin, *pb = io + cin + pout;
+      const ArenaPack ap = arena_pack(p);
+      hipStream_t s = ctx->stream;
+      StageRun sr(stager(ctx));
+      std::vector<HostPiece> pcs;
+      for (uint64_t k0 = 0; k0 < h.K; k0 += kc) {
+        const uint64_t kn = std::min<uint64_t>(kc, h.K - k0);
+        h.pieces(k0, kn, p, pcs);
+        sr.s.h2dv(h.packed ? pb : cb, pcs.data(), pcs.size(), s);
+        if (h.packed) launch_blob_unpack((const uint32_t*)pb, kn, p.L, p.logN, ap, (uint64_t*)cb, s);
+        partial_decrypt_locked(ctx, (const uint64_t*)cb, kn, p.L, lead != 0, (uint64_t*)ob, s);
+        SHELFI_HIP(hipMemcpy(res.p + sizeof(BlobHeader) + k0 * poly_bytes, ob, kn * poly_bytes,
+                             hipMemcpyDeviceToHost));
+      }
+      sr.finish();
+    }
+    *out = res.p;
+    *out_len = total;
+    res.p = nullptr;
+  });
+}
+
+// mkhe.cpp:402 MultipartyDecryptFusion: P parties' "SHPD" partial decryptions of one ciphertext batch ->
+// n doubles.  Needs no keys (the fusing party is the server); the scale comes from the headers.
+int shelfi_fuse_decrypt(shelfi_ctx* ctx, const uint8_t* const* partials, const size_t* lens, size_t P, size_t n,
+                        double* out) {
+  if (!ctx || (n && !out)) return SHELFI_ERR_ARG;
+  if (!partials || !lens || P < 1 || P > (size_t)kMaxCommRanks) {
+    set_error("fuseDecrypt: 1..16 partial decryptions");
+    return SHELFI_ERR_ARG;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    const Params& p = ctx->p;
+    std::vector<BlobHeader> hs(P);
+    size_t leads = 0;
+    for (size_t i = 0; i < P; ++i) {
+      hs[i] = parse_partial(partials[i], lens[i], ctx);
+      leads += hs[i].level;
+      if (hs[i].key_id != hs[0].key_id || hs[i].K != hs[0].K || hs[i].depth != hs[0].depth ||
+          hs[i].scale != hs[0].scale || hs[i].batch != hs[0].batch)
+        throw Error{SHELFI_ERR_FORMAT, "fuseDecrypt: the partial decryptions do not belong to one ciphertext batch"};
+    }
+    if (leads != 1) throw Error{SHELFI_ERR_FORMAT, "fuseDecrypt: exactly one partial decryption must be the lead's"};
+    if (hs[0].batch != p.batch) throw Error{SHELFI_ERR_FORMAT, "fuseDecrypt: batch size differs from the context's"};
+    const uint64_t K = hs[0].K;
+    if (n > K * (uint64_t)p.batch)
+      throw Error{SHELFI_ERR_ARG, "fuseDecrypt: data_dimensions exceeds the slots in the ciphertexts"};
+    if (!n) return;
+    DeviceGuard g(ctx->device);
+    const uint64_t Kn = (n + p.batch - 1) / p.batch;
+    const size_t poly_bytes = (size_t)p.L * p.N * 8;
+    const uint64_t kc = std::min<uint64_t>(Kn, std::max<uint64_t>(1, (64ull << 20) / (P * poly_bytes)));
+    const size_t pin = kc * poly_bytes, dout = kc * p.batch * 8;
+    uint8_t* io = (uint8_t*)ensure(ctx->io, ctx->io_bytes, P * pin + dout);
+    double* ob = (double*)(io + P * pin);
+    hipStream_t s = ctx->stream;
+    // the call's chunks each run the device driver: one redo and one logError (the maximum) per call
+    const uint64_t redo0 = ctx->decode_redo_count;
+    int log_error = -1;
+    for (uint64_t k0 = 0; k0 < Kn; k0 += kc) {
+      const uint64_t kn = std::min<uint64_t>(kc, Kn - k0);
+      const uint64_t o0 = k0 * p.batch, on = std::min<uint64_t>(n - o0, kn * p.batch);
+      FuseIn fz{};
+      fz.P = (uint32_t)P;
+      for (size_t i = 0; i < P; ++i) {
+        SHELFI_HIP(hipMemcpyAsync(io + i * pin, partials[i] + sizeof(BlobHeader) + k0 * poly_bytes, kn * poly_bytes,
+                                  hipMemcpyHostToDevice, s));
+        fz.part[i] = (const uint64_t*)(io + i * pin);
+      }
+      dev_decrypt_locked(ctx, nullptr, kn, p.L, hs[0].scale, on, ob, s, false, &fz);
+      SHELFI_HIP(hipMemcpy(out + o0, ob, on * 8, hipMemcpyDeviceToHost));
+      if (ctx->log_error_pending && Kn > kc) {
+        SHELFI_HIP(hipMemcpy(ctx->host_flag + 2, ctx->dev_flag + 2, 4, hipMemcpyDeviceToHost));
+        log_error = std::max(log_error, (int)ctx->host_flag[2]);
+        ctx->last_log_error = log_error;
+        ctx->log_error_pending = false;
+      }
+    }
+    if (ctx->decode_redo_count > redo0) ctx->decode_redo_count = redo0 + 1;
+  });
+}
+
 }  // extern "C"

@@ -12,6 +12,7 @@
 // operation is a kernel in kernels.hip.
 #include <sys/random.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -693,6 +694,7 @@ int shelfi_set_seed(shelfi_ctx* ctx, uint64_t seed) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   ctx->seed = seed;
   ctx->enc_counter = 0;
+  ctx->thr_counter = 0;
   return SHELFI_OK;
 }
 
@@ -761,6 +763,53 @@ int shelfi_keygen(shelfi_ctx* ctx, const char* cryptodir) {
     ctx->pal_ctx_obj = palisade_context_object(cp, 3);
     ctx->pal_keytag = std::move(tag);
   });
+}
+
+int shelfi_multiparty_keygen(shelfi_ctx* ctx, const uint64_t* prev_pk) {
+  if (!ctx || !prev_pk) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    DeviceGuard g(ctx->device);
+    const Params& p = ctx->p;
+    const size_t LN = (size_t)p.L * p.N;
+    for (size_t i = 0; i < 2 * LN; ++i)
+      if (prev_pk[i] >= p.q[(i / p.N) % p.L]) throw Error{SHELFI_ERR_FORMAT, "previous public key residue >= q"};
+    uint32_t key[8];
+    KeyWiper wipe(key);
+    if (ctx->seed)
+      seed_to_key(ctx->seed, key);
+    else
+      os_random(key, 32);
+    struct Bufs {
+      void* sk = nullptr;
+      void* pk = nullptr;
+      void* prev = nullptr;
+      ~Bufs() {
+        (void)hipFree(sk);
+        (void)hipFree(pk);
+        (void)hipFree(prev);
+      }
+    } d;
+    SHELFI_HIP(hipMalloc(&d.sk, LN * 8));
+    SHELFI_HIP(hipMalloc(&d.pk, 2 * LN * 8));
+    SHELFI_HIP(hipMalloc(&d.prev, 2 * LN * 8));
+    void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, keygen_chain_scratch_bytes(p));
+    std::vector<uint64_t> sk(LN), pk(2 * LN);
+    SHELFI_HIP(hipMemcpyAsync(d.prev, prev_pk, 2 * LN * 8, hipMemcpyHostToDevice, ctx->stream));
+    launch_keygen_chain(p, ctx->dt, key, (const uint64_t*)d.prev, (uint64_t*)d.sk, (uint64_t*)d.pk, scratch,
+                        ctx->stream);
+    SHELFI_HIP(hipMemcpyAsync(sk.data(), d.sk, LN * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SHELFI_HIP(hipMemcpyAsync(pk.data(), d.pk, 2 * LN * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SHELFI_HIP(hipStreamSynchronize(ctx->stream));
+    install_keys(ctx, pk.data(), sk.data(), false);
+  });
+}
+
+int shelfi_set_threshold_noise(shelfi_ctx* ctx, double sigma) {
+  if (!ctx || !std::isfinite(sigma) || sigma < 0.0 || sigma > 0x1.0p40) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  ctx->thr_sigma = sigma;
+  return SHELFI_OK;
 }
 
 int shelfi_load(shelfi_ctx* ctx, const char* cryptodir) {

@@ -183,7 +183,49 @@ static uint64_t dev_chunk(uint64_t K, size_t scratch_per_ct) {
 }
 
 // decrypt K ciphertexts of `towers` RNS towers (the context's L, or fewer after ModReduce)
-// (sum_in: residues are uint64 sums of <= 16 canonical residues, folded on load)
+// (sum_in: residues are uint64 sums of <= 16 canonical residues, folded on load; fuse: threshold
+// fusion -- no ciphertexts and no key, the first pass sums fuse->P partial decryptions [K][towers][N]).
+// The caller holds ctx->mu, has selected the device and checked the keys.
+void dev_decrypt_locked(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, double scale, size_t n,
+                        double* out_dev, hipStream_t s, bool sum_in, const FuseIn* fuse) {
+  if (towers < 1 || towers > ctx->p.L) throw Error{SHELFI_ERR_ARG, "tower count out of range for this context"};
+  if (n > (uint64_t)K * ctx->p.batch) throw Error{SHELFI_ERR_ARG, "n exceeds the slots in K ciphertexts"};
+  const uint64_t Kn = (n + ctx->p.batch - 1) / ctx->p.batch;
+  if (!Kn) return;
+  const size_t ct_words = 2ull * towers * ctx->p.N, part_words = (size_t)towers * ctx->p.N;
+  const GenFlag fl = next_gen_flag(ctx);
+  DecodeNoise dn = decode_noise_begin(ctx, Kn, fl);
+  const uint64_t g0 = dn.g0;
+  // one pass over the call: the decode's tower prefix with the fast CRT, or (exact) every tower
+  // through crt_exact_kernel
+  const auto run = [&](bool exact) {
+    const DecodePass pass = decode_pass(ctx, towers, exact);
+    const Params& p = pass.p;
+    const DeviceTables& dt = pass.dt;
+    const uint64_t kc_max = dev_chunk(Kn, decrypt_scratch_bytes(p, 1));
+    void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, decrypt_scratch_bytes(p, kc_max));
+    dn.reset = 1;
+    for (uint64_t k0 = 0; k0 < Kn; k0 += kc_max) {
+      const uint64_t kc = std::min(kc_max, Kn - k0);
+      const uint64_t o0 = k0 * p.batch, on = std::min<uint64_t>(n - o0, kc * p.batch);
+      dn.g0 = g0 + k0;
+      if (fuse) {
+        FuseIn fz = *fuse;
+        for (uint32_t i = 0; i < fz.P; ++i) fz.part[i] += k0 * part_words;
+        launch_decrypt(p, dt, ctx->dk, nullptr, kc, scale, on, out_dev + o0, scratch, s, &dn, false, towers, fl,
+                       exact, &fz);
+      } else {
+        launch_decrypt(p, dt, ctx->dk, ct_dev + k0 * ct_words, kc, scale, on, out_dev + o0, scratch, s, &dn,
+                       sum_in, towers, fl, exact);
+      }
+      dn.reset = 0;  // the flags are reset by the first chunk's flooding only
+    }
+    decode_noise_readback(ctx, dn);
+  };
+  // the wait after the last pass: scratch is reused by the next call
+  decrypt_passes(ctx, fl, dn, run, [&] { SHELFI_HIP(hipStreamSynchronize(s)); });
+}
+
 static int dev_decrypt(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, double scale,
                        size_t n, double* out_dev, void* stream, bool sum_in = false) {
   if (!ctx || (n && (!ct_dev || !out_dev))) return SHELFI_ERR_ARG;
@@ -191,37 +233,39 @@ static int dev_decrypt(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32
   return guarded([&] {
     require_keys(ctx);
     DeviceGuard g(ctx->device);
-    if (towers < 1 || towers > ctx->p.L) throw Error{SHELFI_ERR_ARG, "tower count out of range for this context"};
-    if (n > (uint64_t)K * ctx->p.batch) throw Error{SHELFI_ERR_ARG, "n exceeds the slots in K ciphertexts"};
-    hipStream_t s = (hipStream_t)stream;  // 0 = legacy default stream
-    const uint64_t Kn = (n + ctx->p.batch - 1) / ctx->p.batch;
-    if (!Kn) return;
-    const size_t ct_words = 2ull * towers * ctx->p.N;
-    const GenFlag fl = next_gen_flag(ctx);
-    DecodeNoise dn = decode_noise_begin(ctx, Kn, fl);
-    const uint64_t g0 = dn.g0;
-    // one pass over the call: the decode's tower prefix with the fast CRT, or (exact) every tower
-    // through crt_exact_kernel
-    const auto run = [&](bool exact) {
-      const DecodePass pass = decode_pass(ctx, towers, exact);
-      const Params& p = pass.p;
-      const DeviceTables& dt = pass.dt;
-      const uint64_t kc_max = dev_chunk(Kn, decrypt_scratch_bytes(p, 1));
-      void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, decrypt_scratch_bytes(p, kc_max));
-      dn.reset = 1;
-      for (uint64_t k0 = 0; k0 < Kn; k0 += kc_max) {
-        const uint64_t kc = std::min(kc_max, Kn - k0);
-        const uint64_t o0 = k0 * p.batch, on = std::min<uint64_t>(n - o0, kc * p.batch);
-        dn.g0 = g0 + k0;
-        launch_decrypt(p, dt, ctx->dk, ct_dev + k0 * ct_words, kc, scale, on, out_dev + o0, scratch, s, &dn,
-                       sum_in, towers, fl, exact);
-        dn.reset = 0;  // the flags are reset by the first chunk's flooding only
-      }
-      decode_noise_readback(ctx, dn);
-    };
-    // the wait after the last pass: scratch is reused by the next call
-    decrypt_passes(ctx, fl, dn, run, [&] { SHELFI_HIP(hipStreamSynchronize(s)); });
+    dev_decrypt_locked(ctx, ct_dev, K, towers, scale, n, out_dev, (hipStream_t)stream, sum_in, nullptr);
   });
+}
+
+// Partial decryption of K ciphertexts [K][2][towers][N] with the context's key share and smudging
+// noise (threshold.hip); the noise stream advances by K.  The caller holds ctx->mu, has selected the
+// device and checked the keys.  Synchronises s (the noise's scratch is reused by the next call).
+void partial_decrypt_locked(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, bool lead,
+                            uint64_t* out_dev, hipStream_t s) {
+  const Params& p = ctx->p;
+  if (towers < 1 || towers > p.L) throw Error{SHELFI_ERR_ARG, "tower count out of range for this context"};
+  if (!K) return;
+  const double sigma = ctx->thr_sigma;
+  uint32_t key[8] = {};
+  KeyWiper wipe(key);
+  const uint64_t g0 = ctx->thr_counter;
+  ctx->thr_counter += K;
+  if (sigma > 0.0) {
+    if (ctx->seed)
+      seed_to_key(ctx->seed, key);
+    else
+      os_random(key, 32);
+  }
+  const size_t per_ct = partial_decrypt_scratch_bytes(p, towers, 1, sigma);
+  const uint64_t kc_max = per_ct ? dev_chunk(K, per_ct) : K;
+  void* scratch = per_ct ? ensure(ctx->scratch, ctx->scratch_bytes, per_ct * kc_max) : nullptr;
+  const size_t tn = (size_t)towers * p.N;
+  for (uint64_t k0 = 0; k0 < K; k0 += kc_max) {
+    const uint64_t kc = std::min<uint64_t>(kc_max, K - k0);
+    launch_partial_decrypt(p, ctx->dt, ctx->dk, ct_dev + k0 * 2 * tn, kc, towers, lead, out_dev + k0 * tn, scratch,
+                           sigma, key, g0 + k0, s);
+  }
+  SHELFI_HIP(hipStreamSynchronize(s));
 }
 
 }  // namespace shelfi
@@ -511,6 +555,37 @@ int shelfi_dev_decrypt_sum(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, ui
     return SHELFI_ERR_ARG;
   }
   return dev_decrypt(ctx, ct_dev, K, ctx ? ctx->p.L : 0, scale, n, out_dev, stream, true);
+}
+
+int shelfi_dev_partial_decrypt(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, int lead,
+                               uint64_t* out_dev, void* stream) {
+  if (!ctx || (K && (!ct_dev || !out_dev))) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    require_keys(ctx);
+    DeviceGuard g(ctx->device);
+    partial_decrypt_locked(ctx, ct_dev, K, towers, lead != 0, out_dev, (hipStream_t)stream);
+  });
+}
+
+int shelfi_dev_fuse_decrypt(shelfi_ctx* ctx, const uint64_t* const* partials_dev, size_t P, size_t K,
+                            uint32_t towers, double scale, size_t n, double* out_dev, void* stream) {
+  if (!ctx || (n && !out_dev)) return SHELFI_ERR_ARG;
+  if (!partials_dev || P < 1 || P > (size_t)kMaxCommRanks) {
+    set_error("fuse_decrypt: 1..16 partial decryptions");
+    return SHELFI_ERR_ARG;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    FuseIn fz{};
+    fz.P = (uint32_t)P;
+    for (size_t i = 0; i < P; ++i) {
+      if (n && !partials_dev[i]) throw Error{SHELFI_ERR_ARG, "fuse_decrypt: null partial"};
+      fz.part[i] = partials_dev[i];
+    }
+    DeviceGuard g(ctx->device);
+    dev_decrypt_locked(ctx, nullptr, K, towers, scale, n, out_dev, (hipStream_t)stream, false, &fz);
+  });
 }
 
 int shelfi_dev_ntt(shelfi_ctx* ctx, uint64_t* polys_dev, size_t P, int inverse, void* stream) {

@@ -211,6 +211,20 @@ __device__ __forceinline__ int64_t round_half_away(double x) {
   return (int64_t)t;
 }
 // complex helpers: (a+bi)(c+di) = (ac - bd, ad + bc), each op rounded (no FMA).
+// Box-Muller pair from two 32-bit stream words: u1 = (a + 1) 2^-32 in (0, 1], u2 = b 2^-32
+// in [0, 1) (revolutions; the top 24 bits are used).  The transcendental functions run
+// in binary32 (one instruction each): the normals scale noise ~1e-13 of the decoded
+// values, so their 2^-24 relative error moves an output by < 1e-20 (the oracle
+// evaluates them in binary64).
+__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, double& z0, double& z1) {
+  const float u1 = (float)fma((double)a, 0x1.0p-32, 0x1.0p-32);
+  const float u2 = (float)(b >> 8) * 0x1.0p-24f;
+  const float r = __fsqrt_rn(-2.0f * __logf(u1));
+  float sn, cs;
+  __sincosf(6.2831853071795864f * u2, &sn, &cs);
+  z0 = (double)(r * cs);
+  z1 = (double)(r * sn);
+}
 __device__ __forceinline__ double2 cmul(double2 v, double2 w) {
   return make_double2(__dsub_rn(__dmul_rn(v.x, w.x), __dmul_rn(v.y, w.y)),
                       __dadd_rn(__dmul_rn(v.x, w.y), __dmul_rn(v.y, w.x)));

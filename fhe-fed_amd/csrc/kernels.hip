@@ -15,9 +15,12 @@
 //   ntt_fwd_blocks_enc(_ct)  last NTT stages of v, m+e0, e1 + c0 = v*b + (m+e0), c1 = v*a + e1
 //                      (_ct: compile-time shape over per-block twiddle slices)
 //   ntt_inv_blocks(_dec_ct)  (decrypt) c0 + c1*s formed on load (ckks.cpp:189) + first INTT stages
+//                      (their FuseIn forms: the threshold fusion's sum of partial decryptions instead,
+//                      mkhe.cpp:402; the partial decryption itself is threshold.hip)
 //   ntt_inv_cols_crt   last INTT stages fused with the exact centered CRT -> double / scale
 //   crt_decode_kernel  the CRT alone (shapes the fused kernel does not cover)
 //   keygen_*           ternary s, Gaussian e, uniform a; b = e - a*s
+//   keygen_chain_*     the threshold key chain's step: b = prev.b + e - a*s over prev.a (mkhe.cpp:282)
 //
 // 64-bit modular arithmetic: CDNA4 has no 64x64->128 multiply; products are
 // built from v_mad_u64_u32 / v_mul_hi_u32 by the compiler (__umul64hi).  Constant
@@ -481,7 +484,10 @@ __global__ __launch_bounds__(256) void ntt_fwd_blocks_enc_pp(
 // (shelfi_dev_combine_arena with fold = 0): c0 is reduced on load (red_any, [0, 2q)), c1 needs
 // nothing (the lazy Shoup product takes any 64-bit multiplicand) — the mod-q fold of the
 // combine happens here instead of in a separate pass over the share.
-template <int BL, int K1, int K2, int K3, int K4, bool SUM = false>
+// FZ = FuseIn (threshold fusion, mkhe.cpp:402): no ciphertext and no key -- the input is the sum of
+// fz.P partial decryptions [K][ctL][N], added as uint64 words while they load (<= 16 canonical
+// residues) and folded by the SUM reduction; the c1*s product is skipped.
+template <int BL, int K1, int K2, int K3, int K4, bool SUM = false, class FZ = NoFuse>
 __global__ __launch_bounds__(256) void ntt_inv_blocks_dec_ct(uint64_t* __restrict__ dbuf, uint32_t L,
                                                              uint32_t logN,
                                                              const ulonglong2* __restrict__ twb,
@@ -489,8 +495,10 @@ __global__ __launch_bounds__(256) void ntt_inv_blocks_dec_ct(uint64_t* __restric
                                                              const uint64_t* __restrict__ ct,
                                                              const uint64_t* __restrict__ sk,
                                                              const uint64_t* __restrict__ sksh,
-                                                             uint32_t xg, uint32_t ctL) {
+                                                             uint32_t xg, uint32_t ctL, FZ fz) {
   static_assert(K1 + K2 + K3 + K4 == BL, "chunk plan must cover the block");
+  constexpr bool FUSE = std::is_same<FZ, FuseIn>::value;
+  static_assert(!FUSE || SUM, "the fused partials are folded by the SUM reduction");
   __shared__ __attribute__((aligned(16))) uint64_t sm[lpad_size(BL)];
   const uint32_t sstart = logN - BL;
   const uint32_t bid = xcd_block(blockIdx.x, xg);
@@ -511,8 +519,16 @@ __global__ __launch_bounds__(256) void ntt_inv_blocks_dec_ct(uint64_t* __restric
   // first chunk: contiguous sets of 2^K1 (T0 = 0)
   inv_chunk_ct<BL, 0, K1, false>(tb, q, n8q,
                           [&](uint32_t j, uint32_t) {
-                            const uint64_t a0 = SUM ? red_any(c0[j], cst) : c0[j];
-                            return csub_neg(a0 + shoup_lazy(c1[j], s[j], ss[j], q), n4q);
+                            if constexpr (FUSE) {
+                              // the first two partials as independent loads (P = 2: no dependent chain)
+                              const uint64_t e = (uint64_t)k * CLN + off + j;
+                              uint64_t a = fz.part[0][e] + (fz.P > 1 ? fz.part[1][e] : 0);
+                              for (uint32_t i = 2; i < fz.P; ++i) a += fz.part[i][e];
+                              return red_any(a, cst);
+                            } else {
+                              const uint64_t a0 = SUM ? red_any(c0[j], cst) : c0[j];
+                              return csub_neg(a0 + shoup_lazy(c1[j], s[j], ss[j], q), n4q);
+                            }
                           },
                           [&](int, uint32_t, uint32_t pj0, auto& x) {
 #pragma unroll
@@ -550,7 +566,9 @@ __global__ __launch_bounds__(256) void ntt_inv_blocks_dec_ct(uint64_t* __restric
 // WL: as ntt_fwd_blocks_enc_pp's, mirrored: the first three chunks (half-sizes 1 .. 2^(BL-K4-1))
 // stay inside 512-element sub-blocks, each wave's own once the first chunk's sets are dealt as
 // g = 2 * 64 w + 64 r + lane; only the exchange into the last chunk crosses waves.
-template <int BL, int K1, int K2, int K3, int K4, bool SUM = false, bool WL = false>
+// FZ = FuseIn: as ntt_inv_blocks_dec_ct's.  No key words are held; the prefetch issues partials 0 and 1 of
+// the next ciphertext as it issues c0 and c1 (added when consumed) and sums partials 2 .. P-1 itself.
+template <int BL, int K1, int K2, int K3, int K4, bool SUM = false, bool WL = false, class FZ = NoFuse>
 __global__ __launch_bounds__(256) void ntt_inv_blocks_dec_pp(uint64_t* __restrict__ dbuf, uint32_t L,
                                                              uint32_t logN,
                                                              const ulonglong2* __restrict__ twb,
@@ -558,8 +576,10 @@ __global__ __launch_bounds__(256) void ntt_inv_blocks_dec_pp(uint64_t* __restric
                                                              const uint64_t* __restrict__ ct,
                                                              const uint64_t* __restrict__ sk,
                                                              const uint64_t* __restrict__ sksh, uint32_t K,
-                                                             uint32_t per_combo, uint32_t ctL) {
+                                                             uint32_t per_combo, uint32_t ctL, FZ fz) {
   static_assert(K1 + K2 + K3 + K4 == BL, "chunk plan must cover the block");
+  constexpr bool FUSE = std::is_same<FZ, FuseIn>::value;
+  static_assert(!FUSE || SUM, "the fused partials are folded by the SUM reduction");
   constexpr int M1 = 1 << K1, NS1 = (1 << (BL - K1)) / 256;
   static_assert(!WL || (BL == 11 && K1 == 2 && K2 == 3 && K3 == 3 && K4 == 3), "wave-local plan");
   __shared__ __attribute__((aligned(16))) ulonglong2 tws[1 << BL];
@@ -582,26 +602,75 @@ __global__ __launch_bounds__(256) void ntt_inv_blocks_dec_pp(uint64_t* __restric
   }
   // first chunk (T0 = 0): set r of this thread = elements (tid + 256 r) 2^K1 + m
   uint64_t sv[NS1][M1], sw[NS1][M1], p0[NS1][M1], p1[NS1][M1];
-#pragma unroll
-  for (int r = 0; r < NS1; ++r)
-#pragma unroll
-    for (int m = 0; m < M1; ++m) {
-      const uint32_t j = (first_g(r) << K1) + m;
-      sv[r][m] = sk[off + j];
-      sw[r][m] = sksh[off + j];
-    }
-  uint32_t k = blockIdx.x / ncombo;
-  const uint64_t CLN = (uint64_t)ctL << logN;  // the ciphertexts' towers (>= L, decode_towers)
-  const auto fetch = [&](uint32_t kk) {
-    const uint64_t* __restrict__ c0 = ct + (uint64_t)kk * 2 * CLN + off;
+  uint64_t p2[FUSE ? NS1 : 1][FUSE ? M1 : 1];  // FUSE: the sum of partials 2 .. P-1
+  if constexpr (!FUSE) {
 #pragma unroll
     for (int r = 0; r < NS1; ++r)
 #pragma unroll
       for (int m = 0; m < M1; ++m) {
         const uint32_t j = (first_g(r) << K1) + m;
-        p0[r][m] = __builtin_nontemporal_load(c0 + j);
-        p1[r][m] = __builtin_nontemporal_load(c0 + CLN + j);
+        sv[r][m] = sk[off + j];
+        sw[r][m] = sksh[off + j];
       }
+  }
+  uint32_t k = blockIdx.x / ncombo;
+  const uint64_t CLN = (uint64_t)ctL << logN;  // the ciphertexts' towers (>= L, decode_towers)
+  const auto fetch = [&](uint32_t kk) {
+    if constexpr (FUSE) {
+      // partials 2 .. P-1 are summed here, two loads in flight per element (their waits sit in the
+      // prefetch); partials 0 and 1 are then only issued, like c0 and c1, and land while the previous
+      // ciphertext is transformed -- P = 2 waits for nothing here
+      const uint64_t eoff = (uint64_t)kk * CLN + off;
+#pragma unroll
+      for (int r = 0; r < NS1; ++r)
+#pragma unroll
+        for (int m = 0; m < M1; ++m) p2[r][m] = 0;
+      uint32_t i = 2;
+      for (; i + 1 < fz.P; i += 2) {
+        const uint64_t* __restrict__ pa = fz.part[i] + eoff;
+        const uint64_t* __restrict__ pb = fz.part[i + 1] + eoff;
+        uint64_t ta[NS1][M1], tb[NS1][M1];
+#pragma unroll
+        for (int r = 0; r < NS1; ++r)
+#pragma unroll
+          for (int m = 0; m < M1; ++m) {
+            const uint32_t j = (first_g(r) << K1) + m;
+            ta[r][m] = __builtin_nontemporal_load(pa + j);
+            tb[r][m] = __builtin_nontemporal_load(pb + j);
+          }
+#pragma unroll
+        for (int r = 0; r < NS1; ++r)
+#pragma unroll
+          for (int m = 0; m < M1; ++m) p2[r][m] += ta[r][m] + tb[r][m];
+      }
+      if (i < fz.P) {
+        const uint64_t* __restrict__ pa = fz.part[i] + eoff;
+#pragma unroll
+        for (int r = 0; r < NS1; ++r)
+#pragma unroll
+          for (int m = 0; m < M1; ++m) p2[r][m] += __builtin_nontemporal_load(pa + ((first_g(r) << K1) + m));
+      }
+      const uint64_t* __restrict__ q0 = fz.part[0] + eoff;
+      const uint64_t* __restrict__ q1 = fz.part[fz.P > 1 ? 1 : 0] + eoff;
+#pragma unroll
+      for (int r = 0; r < NS1; ++r)
+#pragma unroll
+        for (int m = 0; m < M1; ++m) {
+          const uint32_t j = (first_g(r) << K1) + m;
+          p0[r][m] = __builtin_nontemporal_load(q0 + j);
+          p1[r][m] = __builtin_nontemporal_load(q1 + j);
+        }
+    } else {
+      const uint64_t* __restrict__ c0 = ct + (uint64_t)kk * 2 * CLN + off;
+#pragma unroll
+      for (int r = 0; r < NS1; ++r)
+#pragma unroll
+        for (int m = 0; m < M1; ++m) {
+          const uint32_t j = (first_g(r) << K1) + m;
+          p0[r][m] = __builtin_nontemporal_load(c0 + j);
+          p1[r][m] = __builtin_nontemporal_load(c0 + CLN + j);
+        }
+    }
   };
   if (k < K) fetch(k);
   __syncthreads();  // the twiddle slice is in LDS
@@ -613,8 +682,12 @@ __global__ __launch_bounds__(256) void ntt_inv_blocks_dec_pp(uint64_t* __restric
     for (int r = 0; r < NS1; ++r)
 #pragma unroll
       for (int m = 0; m < M1; ++m) {
-        const uint64_t a0 = SUM ? red_any(p0[r][m], cst) : p0[r][m];
-        x[r][m] = csub_neg(a0 + shoup_lazy(p1[r][m], sv[r][m], sw[r][m], q), n4q);
+        if constexpr (FUSE) {
+          x[r][m] = red_any(p0[r][m] + (fz.P > 1 ? p1[r][m] : 0) + p2[r][m], cst);
+        } else {
+          const uint64_t a0 = SUM ? red_any(p0[r][m], cst) : p0[r][m];
+          x[r][m] = csub_neg(a0 + shoup_lazy(p1[r][m], sv[r][m], sw[r][m], q), n4q);
+        }
       }
     if (k + per_combo < K) fetch(k + per_combo);  // lands while this ciphertext is transformed
 #pragma unroll
@@ -702,6 +775,8 @@ static uint32_t pp_per_combo(uint32_t ncombo, uint64_t K, uint32_t per_cu) {
 // register columns (ntt_inv_cols), scaled by N^-1 in the last pass.
 // With ct != nullptr the input is decrypt's c0 + c1*s (ckks.cpp:189), formed while
 // filling LDS from the ciphertext batch [K][2][L][N] (poly p = k*L + t).
+// FZ = FuseIn: the input is the sum of fz.P partial decryptions [K][ctL][N] instead (no key).
+template <class FZ = NoFuse>
 __global__ __launch_bounds__(256) void ntt_inv_blocks(uint64_t* __restrict__ polys, uint32_t L,
                                                       uint32_t logN, uint32_t blkLog,
                                                       const uint64_t* __restrict__ tw,
@@ -711,7 +786,8 @@ __global__ __launch_bounds__(256) void ntt_inv_blocks(uint64_t* __restrict__ pol
                                                       const uint64_t* __restrict__ ct,
                                                       const uint64_t* __restrict__ sk,
                                                       const uint64_t* __restrict__ sksh, int sum_in,
-                                                      uint32_t ctL) {
+                                                      uint32_t ctL, FZ fz) {
+  constexpr bool FUSE = std::is_same<FZ, FuseIn>::value;
   extern __shared__ __attribute__((aligned(16))) uint64_t sm[];
   const uint32_t N = 1u << logN, blk = 1u << blkLog;
   const uint32_t sh = logN - blkLog, nb = 1u << sh;
@@ -721,7 +797,18 @@ __global__ __launch_bounds__(256) void ntt_inv_blocks(uint64_t* __restrict__ pol
   const TowerConst& c = tcs[t];
   const uint64_t q = c.q;
   uint64_t* __restrict__ a = polys + poly * N + ((uint64_t)b << blkLog);
-  if (ct) {
+  if constexpr (FUSE) {
+    const uint64_t e0 = ((poly / L) * ctL << logN) + ((uint64_t)t << logN) + ((uint64_t)b << blkLog);
+    for (uint32_t p = threadIdx.x; p < blk / 2; p += 256) {
+      ulonglong2 x = make_ulonglong2(0, 0);
+      for (uint32_t i = 0; i < fz.P; ++i) {
+        const ulonglong2 y = reinterpret_cast<const ulonglong2*>(fz.part[i] + e0)[p];
+        x.x += y.x;
+        x.y += y.y;
+      }
+      lds_put2(sm, p, make_ulonglong2(red64(x.x, q, c.one_shoup), red64(x.y, q, c.one_shoup)));
+    }
+  } else if (ct) {
     const uint64_t kk = poly / L, off = ((uint64_t)t << logN) + ((uint64_t)b << blkLog);
     const ulonglong2* c0 = reinterpret_cast<const ulonglong2*>(ct + (kk * 2 * ctL << logN) + off);
     const ulonglong2* c1 = reinterpret_cast<const ulonglong2*>(ct + ((kk * 2 + 1) * ctL << logN) + off);
@@ -899,9 +986,10 @@ void launch_ntt(uint64_t* polys, uint64_t P, uint32_t L, uint32_t logN, bool inv
       hipLaunchKernelGGL((ntt_inv_blocks_ct<12, 3, 3, 3, 3>), dim3((uint32_t)nbBlocks), dim3(256), 0, s, polys, L,
                          logN, dt.tw_inv_blk, dt.tc);
     else
-      hipLaunchKernelGGL(ntt_inv_blocks, dim3((uint32_t)nbBlocks), dim3(256), lds, s, polys, L,
+      hipLaunchKernelGGL(ntt_inv_blocks<>, dim3((uint32_t)nbBlocks), dim3(256), lds, s, polys, L,
                          logN, blkLog, dt.ipsi_rev, dt.ipsi_rev_sh, dt.tc, logR == 0 ? 1 : 0,
-                         (const uint64_t*)nullptr, (const uint64_t*)nullptr, (const uint64_t*)nullptr, 0, L);
+                         (const uint64_t*)nullptr, (const uint64_t*)nullptr, (const uint64_t*)nullptr, 0, L,
+                         NoFuse{});
     if (logR > 0) {
       NTT_DISPATCH(logR, ntt_inv_cols, dim3((uint32_t)nbCols), dim3(256), 0, s, polys, L, logN,
                    dt.ipsi_rev, dt.ipsi_rev_sh, dt.tc);
@@ -2429,20 +2517,7 @@ __device__ __forceinline__ double block_sum_1024(double v, double* red) {
   return s;
 }
 
-// Box-Muller pair from two 32-bit stream words: u1 = (a + 1) 2^-32 in (0, 1], u2 = b 2^-32
-// in [0, 1) (revolutions; the top 24 bits are used).  The transcendental functions run
-// in binary32 (one instruction each): the normals scale noise ~1e-13 of the decoded
-// values, so their 2^-24 relative error moves an output by < 1e-20 (the oracle
-// evaluates them in binary64).
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, double& z0, double& z1) {
-  const float u1 = (float)fma((double)a, 0x1.0p-32, 0x1.0p-32);
-  const float u2 = (float)(b >> 8) * 0x1.0p-24f;
-  const float r = __fsqrt_rn(-2.0f * __logf(u1));
-  float sn, cs;
-  __sincosf(6.2831853071795864f * u2, &sn, &cs);
-  z0 = (double)(r * cs);
-  z1 = (double)(r * sn);
-}
+// (box_muller: dev_common.h)
 // (re, im) normals of FFT-input position P: ChaCha20 block P >> 3 (nonce (3 << 56) | g),
 // stream words 2 (P mod 8) and 2 (P mod 8) + 1 (one u64 of chacha20_block's output).
 __device__ __forceinline__ void flood_pair(uint64_t w, double& z0, double& z1) {
@@ -2953,7 +3028,7 @@ size_t decrypt_scratch_bytes(const Params& p, uint64_t K) {
 void launch_decrypt(const Params& p, const DeviceTables& dt, const DeviceKeys& dk,
                     const uint64_t* ct, uint64_t K, double scale, uint64_t n, double* out,
                     void* scratch, hipStream_t s, const DecodeNoise* dn, bool sum_in, uint32_t ct_L,
-                    GenFlag crt_flag, bool exact) {
+                    GenFlag crt_flag, bool exact, const FuseIn* fuse_in) {
   if (!K) return;
   if (!ct_L) ct_L = p.L;
   if (ct_L < p.L) throw Error{SHELFI_ERR_ARG, "decrypt: fewer ciphertext towers than decoded towers"};
@@ -2981,34 +3056,58 @@ void launch_decrypt(const Params& p, const DeviceTables& dt, const DeviceKeys& d
     // prologue is not amortised and the one-shot pass is faster (same dbuf bits)
     const bool pp = logR > 0 && blkLog == 11 && dt.red_ok && switches().dec_pp &&
                     K * ((uint64_t)p.L << logR) >= kDecPpMinItems;
-    if (pp) {
+    const uint64_t* const nokey = nullptr;
+    if (fuse_in) {  // threshold fusion: the same first-pass choice, reading the partials (ct, dk unused)
+      const FuseIn fz = *fuse_in;
+      if (pp) {
+        const uint32_t ncombo = p.L << logR;
+        const uint32_t pc = pp_per_combo(ncombo, K, 3);
+        if (ntt_wave_local())
+          hipLaunchKernelGGL((ntt_inv_blocks_dec_pp<11, 2, 3, 3, 3, true, true, FuseIn>), dim3(ncombo * pc), dim3(256),
+                             0, s, dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, nokey, nokey, nokey, (uint32_t)K, pc, ct_L,
+                             fz);
+        else
+          hipLaunchKernelGGL((ntt_inv_blocks_dec_pp<11, 2, 3, 3, 3, true, false, FuseIn>), dim3(ncombo * pc),
+                             dim3(256), 0, s, dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, nokey, nokey, nokey,
+                             (uint32_t)K, pc, ct_L, fz);
+      } else if (logR > 0 && blkLog == 11 && dt.red_ok)
+        hipLaunchKernelGGL((ntt_inv_blocks_dec_ct<11, 2, 3, 3, 3, true, FuseIn>), dim3((uint32_t)nbBlocks), dim3(256),
+                           0, s, dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, nokey, nokey, nokey, xg, ct_L, fz);
+      else if (logR > 0 && blkLog == 12 && dt.red_ok)
+        hipLaunchKernelGGL((ntt_inv_blocks_dec_ct<12, 3, 3, 3, 3, true, FuseIn>), dim3((uint32_t)nbBlocks), dim3(256),
+                           0, s, dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, nokey, nokey, nokey, xg, ct_L, fz);
+      else
+        hipLaunchKernelGGL(ntt_inv_blocks<FuseIn>, dim3((uint32_t)nbBlocks), dim3(256), sizeof(uint64_t) << blkLog,
+                           s, dbuf, p.L, p.logN, blkLog, dt.ipsi_rev, dt.ipsi_rev_sh, dt.tc, logR == 0 ? 1 : 0,
+                           nokey, nokey, nokey, 0, ct_L, fz);
+    } else if (pp) {
       const uint32_t ncombo = p.L << logR;
       const uint32_t pc = pp_per_combo(ncombo, K, 3);
       if (sum_in)
         hipLaunchKernelGGL((ntt_inv_blocks_dec_pp<11, 2, 3, 3, 3, true>), dim3(ncombo * pc), dim3(256), 0, s, dbuf,
-                           p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, (uint32_t)K, pc, ct_L);
+                           p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, (uint32_t)K, pc, ct_L, NoFuse{});
       else if (ntt_wave_local())
         hipLaunchKernelGGL((ntt_inv_blocks_dec_pp<11, 2, 3, 3, 3, false, true>), dim3(ncombo * pc), dim3(256), 0, s,
-                           dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, (uint32_t)K, pc, ct_L);
+                           dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, (uint32_t)K, pc, ct_L, NoFuse{});
       else
         hipLaunchKernelGGL((ntt_inv_blocks_dec_pp<11, 2, 3, 3, 3, false>), dim3(ncombo * pc), dim3(256), 0, s, dbuf,
-                           p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, (uint32_t)K, pc, ct_L);
+                           p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, (uint32_t)K, pc, ct_L, NoFuse{});
     } else if (logR > 0 && blkLog == 11 && dt.red_ok && !sum_in)
       hipLaunchKernelGGL((ntt_inv_blocks_dec_ct<11, 2, 3, 3, 3>), dim3((uint32_t)nbBlocks), dim3(256), 0,
-                         s, dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, xg, ct_L);
+                         s, dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, xg, ct_L, NoFuse{});
     else if (logR > 0 && blkLog == 11 && dt.red_ok)
       hipLaunchKernelGGL((ntt_inv_blocks_dec_ct<11, 2, 3, 3, 3, true>), dim3((uint32_t)nbBlocks), dim3(256), 0,
-                         s, dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, xg, ct_L);
+                         s, dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, xg, ct_L, NoFuse{});
     else if (logR > 0 && blkLog == 12 && dt.red_ok && !sum_in)
       hipLaunchKernelGGL((ntt_inv_blocks_dec_ct<12, 3, 3, 3, 3>), dim3((uint32_t)nbBlocks), dim3(256), 0,
-                         s, dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, xg, ct_L);
+                         s, dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, xg, ct_L, NoFuse{});
     else if (logR > 0 && blkLog == 12 && dt.red_ok)
       hipLaunchKernelGGL((ntt_inv_blocks_dec_ct<12, 3, 3, 3, 3, true>), dim3((uint32_t)nbBlocks), dim3(256), 0,
-                         s, dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, xg, ct_L);
+                         s, dbuf, p.L, p.logN, dt.tw_inv_blk, dt.tc, ct, dk.sk, dk.sk_sh, xg, ct_L, NoFuse{});
     else
-      hipLaunchKernelGGL(ntt_inv_blocks, dim3((uint32_t)nbBlocks), dim3(256), sizeof(uint64_t) << blkLog,
+      hipLaunchKernelGGL(ntt_inv_blocks<>, dim3((uint32_t)nbBlocks), dim3(256), sizeof(uint64_t) << blkLog,
                          s, dbuf, p.L, p.logN, blkLog, dt.ipsi_rev, dt.ipsi_rev_sh, dt.tc,
-                         logR == 0 ? 1 : 0, ct, dk.sk, dk.sk_sh, sum_in ? 1 : 0, ct_L);
+                         logR == 0 ? 1 : 0, ct, dk.sk, dk.sk_sh, sum_in ? 1 : 0, ct_L, NoFuse{});
     if (logR > 0 && fuse) {
       const uint64_t nbf = K * ((p.N >> logR) / 64);
 #define CRT_FUSED(LR, NCC, EDGE)                                                                              \
@@ -3208,6 +3307,44 @@ void launch_keygen(const Params& p, const DeviceTables& dt, const uint32_t key[8
   const uint64_t LN = (uint64_t)p.L * p.N;
   hipLaunchKernelGGL(keygen_combine_kernel, dim3((uint32_t)((LN + 255) / 256)), dim3(256), 0, s,
                      se, p.logN, p.L, dt.tc, sk, pk);
+  SHELFI_HIP(hipGetLastError());
+}
+
+// One step of the threshold key chain (mkhe.cpp:282 MultipartyKeyGen): sk = NTT(s);
+// b = prev.b + NTT(e) - a * NTT(s) with a = prev.a (prev [2][L][N]: b, a).
+__global__ __launch_bounds__(256) void keygen_chain_combine_kernel(const uint64_t* __restrict__ se, uint32_t logN,
+                                                                   uint32_t L, const TowerConst* __restrict__ tcs,
+                                                                   const uint64_t* __restrict__ prev,
+                                                                   uint64_t* __restrict__ sk,
+                                                                   uint64_t* __restrict__ pk) {
+  const uint64_t LN = (uint64_t)L << logN;
+  const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= LN) return;
+  const uint32_t t = (uint32_t)(e >> logN);
+  const TowerConst c = tcs[t];
+  const uint64_t s = se[e], er = se[LN + e], a = prev[LN + e];
+  sk[e] = s;
+  pk[e] = addmod(prev[e], submod(er, mulmod_generic(a, s, c), c.q), c.q);
+  pk[LN + e] = a;
+}
+
+// s, e from keygen's stream ([0, N) and [N, 2N) of nonce 2 << 56); the a it would draw lands in the
+// scratch and is dropped
+size_t keygen_chain_scratch_bytes(const Params& p) { return 3ull * p.L * p.N * sizeof(uint64_t); }
+
+void launch_keygen_chain(const Params& p, const DeviceTables& dt, const uint32_t key[8], const uint64_t* prev_pk,
+                         uint64_t* sk, uint64_t* pk, void* scratch, hipStream_t s) {
+  Key8 k8;
+  for (int i = 0; i < 8; ++i) k8.k[i] = key[i];
+  uint64_t* se = reinterpret_cast<uint64_t*>(scratch);
+  const uint64_t LN = (uint64_t)p.L * p.N;
+  const uint32_t th = p.N / 8;
+  hipLaunchKernelGGL(keygen_sample_kernel, dim3((th + 255) / 256), dim3(256), 0, s, p.logN, p.L, dt.tc, dt.cdt,
+                     dt.cdt_len, k8, se, se + 2 * LN);
+  SHELFI_HIP(hipGetLastError());
+  launch_ntt(se, 2ull * p.L, p.L, p.logN, false, dt, s);
+  hipLaunchKernelGGL(keygen_chain_combine_kernel, dim3((uint32_t)((LN + 255) / 256)), dim3(256), 0, s, se, p.logN,
+                     p.L, dt.tc, prev_pk, sk, pk);
   SHELFI_HIP(hipGetLastError());
 }
 

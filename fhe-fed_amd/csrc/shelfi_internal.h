@@ -241,6 +241,8 @@ struct shelfi_ctx {
   uint64_t params_id = 0;
   uint64_t seed = 0;          // 0 -> OS entropy per call
   uint64_t enc_counter = 0;   // global ciphertext index for the sampler stream
+  double thr_sigma = 1048576.0;  // shelfi_set_threshold_noise: smudging noise of a partial decryption
+  uint64_t thr_counter = 0;      // ciphertexts partially decrypted so far (the noise stream's nonce)
   uint32_t* host_flag = nullptr; // pinned host mirror of dev_flag (async readback before one sync)
   uint32_t* map_flag_host = nullptr;  // GenFlag words in pinned host memory (encode range, decode CRT range)
   uint32_t* map_flag_dev = nullptr;   // the same words as the device addresses them
@@ -386,11 +388,19 @@ struct DecodeNoise {
   GenFlag fail;               // word 3: the precision failure (PALISADE's Decode throws)
   int reset = 1;              // the launch's flooding resets flags [1], [2] first (a call's first chunk)
 };
+// Threshold fusion's input (mkhe.cpp:402 MultipartyDecryptFusion): P partial decryptions [K][ct_L][N],
+// canonical residues, summed mod q_t by decrypt's first INTT pass while it loads them.
+struct FuseIn {
+  const uint64_t* part[kMaxCommRanks];
+  uint32_t P;
+};
+struct NoFuse {};  // the first-pass kernels' ciphertext-and-key form
 void launch_decrypt(const Params& p, const DeviceTables& dt, const DeviceKeys& dk,
                     const uint64_t* ct, uint64_t K, double scale, uint64_t n, double* out,
                     void* scratch, hipStream_t s, const DecodeNoise* dn = nullptr, bool sum_in = false,
                     uint32_t ct_L = 0,  // ct_L: towers of the ciphertexts (0 = p.L; >= p.L)
-                    GenFlag crt_flag = GenFlag{}, bool exact = false);
+                    GenFlag crt_flag = GenFlag{}, bool exact = false,
+                    const FuseIn* fuse_in = nullptr);  // fuse_in: no ct, no dk; ct_L = the partials' towers
 // crt_flag: the fast CRT (crt_value) sets word 2 to crt_flag.gen when a coefficient's centred value is not
 // in (-2^127, 2^127) over these towers -- the caller redoes the call with every tower and exact =
 // true (crt_exact_kernel, any |X| <= (Q - 1) / 2).  A fast-path launch needs crt_flag.
@@ -398,6 +408,17 @@ size_t decrypt_scratch_bytes(const Params& p, uint64_t K);
 void launch_keygen(const Params& p, const DeviceTables& dt, const uint32_t key[8], uint64_t* sk,
                    uint64_t* pk, void* scratch, hipStream_t s);
 size_t keygen_scratch_bytes(const Params& p);
+// threshold key chain step (kernels.hip): prev_pk [2][L][N] (b, a) on the device -> sk, pk
+void launch_keygen_chain(const Params& p, const DeviceTables& dt, const uint32_t key[8], const uint64_t* prev_pk,
+                         uint64_t* sk, uint64_t* pk, void* scratch, hipStream_t s);
+size_t keygen_chain_scratch_bytes(const Params& p);
+// threshold partial decryption (threshold.hip): ct [K][2][towers][N] -> out [K][towers][N] =
+// [c0 +] c1 * sk + NTT(e), e = round(sigma z) per ciphertext (nonce (5 << 56) | (g0 + k)); sigma = 0:
+// no noise, one element-wise pass.  p, dt, dk: the context's (towers <= p.L, a prefix).
+size_t partial_decrypt_scratch_bytes(const Params& p, uint32_t towers, uint64_t K, double sigma);
+void launch_partial_decrypt(const Params& p, const DeviceTables& dt, const DeviceKeys& dk, const uint64_t* ct,
+                            uint64_t K, uint32_t towers, bool lead, uint64_t* out, void* scratch, double sigma,
+                            const uint32_t key[8], uint64_t g0, hipStream_t s);
 
 // dev_api.cpp: the arena aggregation (ctx lock held, weights checked), refused-slot check;
 // call_state.cpp: weights

@@ -70,6 +70,31 @@ static BlobHeader make_header(const shelfi_ctx* ctx, uint64_t K, uint32_t depth,
   return h;
 }
 
+// A partial decryption's blob ("SHPD", api_internal.h); ctx = nullptr: the header and length alone.
+BlobHeader parse_partial(const uint8_t* blob, size_t len, const shelfi_ctx* ctx) {
+  if (!blob || len < sizeof(BlobHeader)) throw Error{SHELFI_ERR_FORMAT, "partial decryption blob too short"};
+  BlobHeader h;
+  std::memcpy(&h, blob, sizeof(h));
+  if (std::memcmp(h.magic, "SHPD", 4) != 0 || h.version != 1 || h.header_bytes != 64)
+    throw Error{SHELFI_ERR_FORMAT, "not a SHELFI partial decryption blob (bad magic/version)"};
+  if (h.L == 0 || h.L > kMaxTowers || h.logN < 10 || h.logN > 17 || h.level > 1)
+    throw Error{SHELFI_ERR_FORMAT, "corrupt partial decryption blob header"};
+  if (ctx && (h.logN != ctx->p.logN || h.L != ctx->p.L || h.params_id != ctx->params_id))
+    throw Error{SHELFI_ERR_FORMAT, "partial decryption was produced under different crypto parameters"};
+  // K comes from an untrusted header: bound it by the payload before multiplying
+  const uint64_t payload = len - sizeof(BlobHeader), ct_bytes = (uint64_t)h.L * (8ull << h.logN);
+  if (h.K > payload / ct_bytes || payload != h.K * ct_bytes)
+    throw Error{SHELFI_ERR_FORMAT, "partial decryption blob length does not match header"};
+  return h;
+}
+
+BlobHeader make_partial_header(const shelfi_ctx* ctx, uint64_t K, uint32_t depth, double scale, bool lead) {
+  BlobHeader h = make_header(ctx, K, depth, scale);
+  std::memcpy(h.magic, "SHPD", 4);
+  h.level = lead ? 1 : 0;
+  return h;
+}
+
 // Packed wire payload sizes (version-2 blobs): bytes of one (ct, poly) group of the first Lu towers.
 uint64_t packed_poly_bytes(const Params& p, uint32_t Lu) {
   const ArenaPack ap = arena_pack(p);
@@ -165,6 +190,55 @@ int shelfi_blob_info(const uint8_t* blob, size_t len, uint64_t* num_cts, uint32_
 }
 
 size_t shelfi_blob_header_bytes(void) { return sizeof(BlobHeader); }
+
+int shelfi_partial_blob_info(const uint8_t* blob, size_t len, uint64_t* num_cts, uint32_t* towers, int* lead,
+                             double* scale, uint64_t* key_id) {
+  return guarded([&] {
+    const BlobHeader h = parse_partial(blob, len, nullptr);
+    if (num_cts) *num_cts = h.K;
+    if (towers) *towers = h.L;
+    if (lead) *lead = (int)h.level;
+    if (scale) *scale = h.scale;
+    if (key_id) *key_id = h.key_id;
+  });
+}
+
+int shelfi_partial_blob_pack(uint32_t ring_dim, uint32_t num_towers, uint32_t batch, uint64_t num_cts,
+                             uint32_t depth, double scale, uint64_t params_id, uint64_t key_id, int lead,
+                             const uint64_t* residues, uint8_t** out, size_t* out_len) {
+  if (!out || !out_len || (num_cts && !residues)) return SHELFI_ERR_ARG;
+  *out = nullptr;
+  *out_len = 0;
+  return guarded([&] {
+    if (ring_dim < 1024 || ring_dim > (1u << 17) || (ring_dim & (ring_dim - 1)) || num_towers < 1 ||
+        num_towers > (uint32_t)kMaxTowers)
+      throw Error{SHELFI_ERR_ARG, "partial blob: ring dimension or tower count out of range"};
+    const uint64_t ct_bytes = (uint64_t)num_towers * ring_dim * 8;
+    if (num_cts > (~0ull - sizeof(BlobHeader)) / ct_bytes) throw Error{SHELFI_ERR_ARG, "partial blob: too large"};
+    BlobHeader h;
+    std::memset(&h, 0, sizeof(h));
+    std::memcpy(h.magic, "SHPD", 4);
+    h.version = 1;
+    h.header_bytes = 64;
+    h.logN = (uint32_t)__builtin_ctz(ring_dim);
+    h.L = num_towers;
+    h.K = num_cts;
+    h.depth = depth;
+    h.level = lead ? 1 : 0;
+    h.scale = scale;
+    h.params_id = params_id;
+    h.key_id = key_id;
+    h.batch = batch;
+    h.encoding = 4;
+    const size_t payload = (size_t)(num_cts * ct_bytes);
+    uint8_t* blob = (uint8_t*)std::malloc(sizeof(h) + payload);
+    if (!blob) throw std::bad_alloc();
+    std::memcpy(blob, &h, sizeof(h));
+    if (payload) std::memcpy(blob + sizeof(h), residues, payload);
+    *out = blob;
+    *out_len = sizeof(h) + payload;
+  });
+}
 
 // Host restatement of blob_unpack_kernel (the packed wire payload): row r of the
 // [K][2][L][N] batch, lane l, field j -> residue 128 (j >> 1) + 2 l + (j & 1).

@@ -399,6 +399,52 @@ int shelfi_dev_decrypt_level(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, 
 int shelfi_dev_decrypt_sum(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t terms, double scale,
                            size_t n, double* out_dev, void* stream);
 
+/* ---- threshold CKKS (the reference's code/mkhe/mkhe.cpp RunCKKS, lines 188-465) ---- *
+ * P parties hold additive shares s_i of one secret key; a ciphertext under the joint public key
+ * decrypts only when every party contributes a partial decryption.  Encrypt and
+ * computeWeightedAverage are unchanged: they work under any public key. */
+/* cc->MultipartyKeyGen(prev.publicKey) (mkhe.cpp:268-282): one step of the key chain.  prev_pk is the
+ * previous party's public key [2][L][N] (b, a); this party keeps a = prev.a, samples s_i (ternary) and
+ * e_i (the context's sigma) from keygen's seeded stream (its a is drawn and dropped) and installs
+ * pk = (prev.b + NTT(e_i) - a NTT(s_i), a), sk = NTT(s_i), in memory only.  The lead party calls
+ * shelfi_keygen(ctx, ""); after the chain every party installs the last public key beside its own
+ * share with shelfi_set_keys(pk_joint, sk_i).  A residue >= q_t: SHELFI_ERR_FORMAT. */
+int shelfi_multiparty_keygen(shelfi_ctx* ctx, const uint64_t* prev_pk);
+/* Standard deviation of the smudging noise every partial decryption adds (PALISADE's MP_SD role;
+ * default 2^20).  0 = parity mode: no noise, deterministic partials.  Negative, non-finite or above
+ * 2^40: SHELFI_ERR_ARG. */
+int shelfi_set_threshold_noise(shelfi_ctx* ctx, double sigma);
+/* cc->MultipartyDecryptLead / MultipartyDecryptMain (mkhe.cpp:395-400) with the context's key share:
+ * ct_dev [K][2][towers][N] -> out_dev [K][towers][N] (EVALUATION), lead = 1: c0 + c1 s_i + NTT(e),
+ * lead = 0: c1 s_i + NTT(e); e = round(sigma z), one integer polynomial per ciphertext from the
+ * context's ChaCha20 stream, nonce (5 << 56) | (g0 + k), g0 a per-context counter that advances by K
+ * with every call.  towers in 1..L as for shelfi_dev_decrypt_level; needs keys; synchronises `stream`. */
+int shelfi_dev_partial_decrypt(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, int lead,
+                               uint64_t* out_dev, void* stream);
+/* cc->MultipartyDecryptFusion (mkhe.cpp:402): partials_dev is a host array of P (1..16) device
+ * pointers, each [K][towers][N]; they are summed mod q_t while decrypt's first pass loads them, and the
+ * rest is shelfi_dev_decrypt_level's chain (tower prefix, range flag and exact redo,
+ * shelfi_set_decode_exact, decode flooding, shelfi_decode_redo_count, shelfi_decode_log_error).
+ * Needs no keys: the fusing party is the server. */
+int shelfi_dev_fuse_decrypt(shelfi_ctx* ctx, const uint64_t* const* partials_dev, size_t P, size_t K,
+                            uint32_t towers, double scale, size_t n, double* out_dev, void* stream);
+/* The same over bytes (mkhe.cpp:395-402).  shelfi_partial_decrypt takes a ciphertext batch in any of the
+ * three wire formats and answers with a partial-decryption blob (magic "SHPD": the ciphertext blob's
+ * 64-byte header, the joint key's key_id, a lead/main mark, K x L x N uint64 residues; free with
+ * shelfi_free).  shelfi_fuse_decrypt takes the scale from the headers and returns SHELFI_ERR_FORMAT
+ * unless params_id, key_id, K, depth and scale agree across the partials and exactly one is the lead's. */
+int shelfi_partial_decrypt(shelfi_ctx* ctx, const uint8_t* blob, size_t len, int lead, uint8_t** out,
+                           size_t* out_len);
+int shelfi_fuse_decrypt(shelfi_ctx* ctx, const uint8_t* const* partials, const size_t* lens, size_t P, size_t n,
+                        double* out);
+/* Host-only: a partial-decryption blob's header (mkhe.cpp:395-400's results as they travel), and the
+ * blob built from host residues [K][num_towers][ring_dim] with the given metadata. */
+int shelfi_partial_blob_info(const uint8_t* blob, size_t len, uint64_t* num_cts, uint32_t* towers, int* lead,
+                             double* scale, uint64_t* key_id);
+int shelfi_partial_blob_pack(uint32_t ring_dim, uint32_t num_towers, uint32_t batch, uint64_t num_cts,
+                             uint32_t depth, double scale, uint64_t params_id, uint64_t key_id, int lead,
+                             const uint64_t* residues, uint8_t** out, size_t* out_len);
+
 /* ---- test hooks (host-visible tables) ------------------------------------- */
 /* CKKS special-FFT twiddles (flat, index lenh + j) as used by the kernels. */
 int shelfi_fft_twiddles(uint32_t slots, double* inv_re, double* inv_im, double* fwd_re,
