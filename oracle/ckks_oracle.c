@@ -1117,6 +1117,51 @@ void or_flood_out_normals(uint64_t seed, uint64_t g, uint32_t S, double* zo) {
   }
 }
 
+/* Smudging noise of a partial decryption, ciphertext g of the context's noise counter (product
+ * spec: DESIGN.md §2.10 "Noise stream" and the header comment of fhe-fed_amd/csrc/threshold.hip).
+ * ChaCha20 under or_seed_to_key(seed), nonce (5 << 56) | g.  One block gives 16 normals: its 64-bit
+ * word u (32-bit words 2u low, 2u + 1 high) is one Box-Muller pair as in or_flood_normals (binary64,
+ * u1 = (w + 1) 2^-32, u2 = w' 2^-32), normal 2u = r cos, normal 2u + 1 = r sin.
+ * With R = 2^(logN - block_log) rows, coefficient j = row 2^block_log + col:
+ *   R = 1: block j >> 4, normal j & 15;
+ *   R > 1: column col owns blocks col nb .. col nb + nb - 1, nb = max(1, R / 16); row r takes
+ *          normal r of them (block col nb + (r >> 4), normal r & 15; a column of fewer than 16 rows
+ *          leaves the rest of its block unused).
+ * e[j] = or_round_half_away(sigma z).  block_log is the NTT block size of the ring (oracle.py's
+ * threshold_block_log).  The product evaluates log / sin / cos in binary32: its integers are close
+ * to these, not equal (tests/test_gpu_threshold_stream.py states the bound). */
+void or_threshold_noise(uint64_t seed, uint64_t g, uint32_t logN, uint32_t block_log, double sigma,
+                        int64_t* e) {
+  uint32_t key[8], blk[16];
+  or_seed_to_key(seed, key);
+  const uint64_t nonce = (5ull << 56) | g;
+  const uint32_t N = 1u << logN, R = 1u << (logN - block_log);
+  const uint32_t nb = R >= 16 ? R / 16 : 1;
+  const uint32_t per = R == 1 ? 16 : (R < 16 ? R : 16); /* normals taken from one block */
+  const uint64_t nblocks = R == 1 ? N / 16 : ((uint64_t)nb << block_log); /* nb per column */
+  for (uint64_t b = 0; b < nblocks; ++b) {
+    or_chacha20_block(key, b, nonce, blk);
+    double z[16];
+    for (uint32_t u = 0; u < 8; ++u) {
+      double u1 = ((double)blk[2 * u] + 1.0) * 0x1.0p-32;
+      double u2 = (double)blk[2 * u + 1] * 0x1.0p-32;
+      double r = sqrt(-2.0 * log(u1));
+      z[2 * u] = r * cos(2.0 * M_PI * u2);
+      z[2 * u + 1] = r * sin(2.0 * M_PI * u2);
+    }
+    for (uint32_t n = 0; n < per; ++n) {
+      uint64_t j;
+      if (R == 1) {
+        j = 16 * b + n;
+      } else {
+        const uint64_t col = b / nb, row = 16 * (b % nb) + n;
+        j = (row << block_log) + col;
+      }
+      e[j] = or_round_half_away(sigma * z[n]);
+    }
+  }
+}
+
 /* decrypt + flooded decode of one ciphertext (seeded stream, ciphertext index g).
  * PALISADE adds N(0, sd) to every coefficient of the symmetrized decryption, then decodes: the
  * decoded slots' real parts carry Re(F z) sd for an i.i.d. standard complex Gaussian vector z of

@@ -92,6 +92,7 @@ def _load():
         "or_sample_encrypt": (None, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, i64p, i64p, i64p]),
         "or_sample_keygen": (None, [C.c_uint64, C.c_uint32, C.c_uint32, u64p, C.c_double, i64p, i64p,
                                     u64p]),
+        "or_threshold_noise": (None, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double, i64p]),
         "or_special_primes": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u32p, u32p, u32p, u64p, u64p]),
         "or_evk_keygen": (None, [C.c_uint64, C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p, u64p,
                                  C.c_uint32, C.c_uint32, C.c_double, u64p, u64p]),
@@ -378,6 +379,26 @@ def sample_keygen(seed: int, N: int, q, sigma: float = SIGMA):
     a = np.zeros((len(q), N), np.uint64)
     lib.or_sample_keygen(seed, N, len(q), _p(q, u64p), sigma, _p(s, i64p), _p(e, i64p), _p(a, u64p))
     return s, e, a
+
+
+def threshold_block_log(logN: int) -> int:
+    """The NTT block size the smudging-noise layout is stated in (DESIGN.md §2.10 "Kernels": rings up
+    to 2^11 are one block, 2^12..2^16 run 2^11 blocks, 2^17 runs 2^12 blocks).  Restated here, not
+    imported from the product."""
+    return 12 if logN >= 17 else min(logN, 11)
+
+
+def threshold_noise(seed: int, g: int, N: int, block_log: int | None = None, sigma: float = 2.0 ** 20) -> np.ndarray:
+    """The smudging-noise integers of a partial decryption's ciphertext g (DESIGN.md §2.10 "Noise
+    stream"; fhe-fed_amd/csrc/threshold.hip's header comment): nonce (5 << 56) | g, 16 normals per
+    ChaCha20 block, R = N / 2^block_log rows; binary64 Box-Muller, e = round_half_away(sigma z)."""
+    logN = int(N).bit_length() - 1
+    assert 1 << logN == N and N >= 16
+    if block_log is None:
+        block_log = threshold_block_log(logN)
+    e = np.zeros(N, np.int64)
+    lib.or_threshold_noise(seed, g, logN, block_log, float(sigma), _p(e, i64p))
+    return e
 
 
 # ------------------------------------------------- end-to-end composition ----

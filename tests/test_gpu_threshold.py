@@ -12,9 +12,11 @@ generic passes behind a columns pass).
 Bit-exact where the arithmetic is deterministic: the chain against the oracle's keygen stream and NTT,
 the sigma = 0 partials against c0 + c1 s_i on the host (Python integers), the fusion against the
 single-key device decrypt of (sum of the partials, 0) and against the oracle's decrypt under sum s_i.
-The smudging noise has no oracle (its sampler is unpinned): it is checked as what it must be --
-one integer polynomial per ciphertext, the same in every tower, of the set standard deviation, never
-repeated, reproducible under a seed.
+The smudging noise is checked here as what it must be -- one integer polynomial per ciphertext, the same in
+every tower, of the set standard deviation, never repeated, reproducible under a seed; its stream is held
+against the oracle's restatement (oracle.threshold_noise) in test_gpu_threshold_stream.py, and the paths
+these K = 2 calls do not take (the persistent fusion pass at every P, switches, chunked calls, levels below
+L, planted extremes) in test_gpu_threshold_paths.py.  PALISADE's own sampler stays unpinned.
 
 Bounds: |mean| <= 5 sigma / sqrt(K N) (5 standard errors); the sample standard deviation within 5% of
 sigma (its own spread at K N >= 4096 samples is below 1.2%; rounding adds 1/12 to the variance, 0.4% at
