@@ -205,6 +205,14 @@ class CKKS(Scheme):
         check(self._lib.shelfi_decode_redo_count(self._ctx, C.byref(n)), "decode_redo_count")
         return int(n.value)
 
+    def encode_redo_count(self) -> int:
+        """Encrypt calls of this context (bytes and device API) whose fast pass met a message
+        coefficient above 2^61 in magnitude and were redone on the large-value path
+        (shelfi_encode_redo_count): one per call, however many of its ciphertexts were flagged."""
+        n = C.c_uint64()
+        check(self._lib.shelfi_encode_redo_count(self._ctx, C.byref(n)), "encode_redo_count")
+        return int(n.value)
+
     def last_log_precision(self):
         """PALISADE Plaintext::GetLogPrecision of the last flooded decrypt (worst
         ciphertext): scaleFactorBits - logError; None if none was flooded."""

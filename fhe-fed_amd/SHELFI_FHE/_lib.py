@@ -111,6 +111,7 @@ SIGNATURES = {
     "shelfi_set_decode_exact": (C.c_int, [C.c_void_p, C.c_int]),
     "shelfi_decode_log_error": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "shelfi_decode_redo_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "shelfi_encode_redo_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "shelfi_encrypt_into": (C.c_int, [C.c_void_p, f64p, C.c_size_t, C.c_void_p, C.c_size_t,
                                       C.POINTER(C.c_size_t)]),
     "shelfi_weighted_average": (C.c_int, [C.c_void_p, C.POINTER(u8p), C.POINTER(C.c_size_t), f32p,

@@ -109,8 +109,10 @@ static void encrypt_bytes_pipeline(shelfi_ctx* ctx, const double* x, size_t n, u
   }
   sr.finish();
   pp.sync();
-  if (!approx && encode_needs_approx(ctx, fl))
+  if (!approx && encode_needs_approx(ctx, fl)) {  // once per call, whichever chunks were flagged
+    ++ctx->encode_redo_count;
     encrypt_bytes_pipeline(ctx, x, n, K, dst, key, g0, true);
+  }
 }
 
 // Validates the learners' batches (same format, params, key, K, depth, scale).

@@ -53,7 +53,8 @@ bool gen_flag_raised(const shelfi_ctx* ctx, const GenFlag& f, int w) {
 }
 
 // The encode range flag of an encrypt call (kernels.hip enc_range_flag): non-finite values are refused;
-// a finite |x Delta| above 2^61 means the call is redone on the large-value path.
+// a finite message coefficient above 2^61 in magnitude means the call is redone on the large-value path
+// (the callers count that in ctx->encode_redo_count).
 bool encode_needs_approx(const shelfi_ctx* ctx, const GenFlag& f) {
   if (gen_flag_raised(ctx, f, 1)) throw Error{SHELFI_ERR_RANGE, "encrypt: non-finite input value"};
   return gen_flag_raised(ctx, f, 0);
@@ -142,6 +143,13 @@ int shelfi_decode_redo_count(shelfi_ctx* ctx, uint64_t* count) {
   if (!ctx || !count) return SHELFI_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   *count = ctx->decode_redo_count;
+  return SHELFI_OK;
+}
+
+int shelfi_encode_redo_count(shelfi_ctx* ctx, uint64_t* count) {
+  if (!ctx || !count) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  *count = ctx->encode_redo_count;
   return SHELFI_OK;
 }
 

@@ -533,7 +533,8 @@ int shelfi_dev_encrypt(shelfi_ctx* ctx, const double* x_dev, size_t n, uint64_t*
       if (approx) break;
       SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
       if (!encode_needs_approx(ctx, fl)) break;
-      approx = true;  // some |x Delta| > 2^61: redo the call on the large-value path
+      approx = true;  // some message coefficient above 2^61: redo the call on the large-value path
+      ++ctx->encode_redo_count;
     }
   });
 }

@@ -268,6 +268,7 @@ struct shelfi_ctx {
   double decode_m_factor = 1.0;
   int decode_exact = 0;          // shelfi_set_decode_exact: every decrypt over every tower, exact CRT
   uint64_t decode_redo_count = 0;  // decrypt calls whose fast pass was redone exactly (shelfi_decode_redo_count)
+  uint64_t encode_redo_count = 0;  // encrypt calls redone on the large-value path (shelfi_encode_redo_count)
   int last_log_error = -1;       // of the last flooded decrypt, -1 if none
   bool log_error_pending = false;  // dev_flag[2] holds a newer one, read on demand (shelfi_decode_log_error)
   std::string pal_ctx_obj;       // PALISADE keys: embedded context object (§8 f1)

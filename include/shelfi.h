@@ -143,6 +143,11 @@ int shelfi_set_decode_exact(shelfi_ctx* ctx, int exact);
  * coefficient outside its range and were redone through the exact CRT.  Calls made under
  * shelfi_set_decode_exact(ctx, 1) have no fast pass and do not count. */
 int shelfi_decode_redo_count(shelfi_ctx* ctx, uint64_t* count);
+/* Encrypt calls of this context (shelfi_encrypt*, shelfi_dev_encrypt) whose fast pass met a message
+ * coefficient above 2^61 in magnitude and were redone on the large-value path (PALISADE's
+ * approxFactor scale-down).  One per call, however many of its ciphertexts or chunks were flagged; a
+ * call refused for a non-finite value does not count. */
+int shelfi_encode_redo_count(shelfi_ctx* ctx, uint64_t* count);
 /* logError of the last flooded decrypt (max over its ciphertexts; PALISADE
  * Plaintext::GetLogError), -1 if none.  Precision = scale_bits - logError. */
 int shelfi_decode_log_error(shelfi_ctx* ctx, int* log_error);

@@ -1,8 +1,11 @@
 """Encode's large-value path on the HIP path (VERDICT r4 missing 1; ckks.cpp:80 ->
-CKKSPackedEncoding::Encode's approxFactor): values with |x Delta| > 2^61 are no
-longer refused.  The fast kernels flag them, and the call is redone with per-ciphertext scale-down
-exponents (kernels.hip launch_encrypt_approx).  Every ciphertext is bit-exact vs the oracle's
-restatement (or_encode_coeffs_ex), and decrypts within 2^-40 relative of the input.
+CKKSPackedEncoding::Encode's approxFactor): values whose message coefficients
+round(FFTSpecialInv(x)_i / S * Delta) exceed 2^61 are no longer refused.  The fast kernels flag such a
+coefficient (not |x Delta|: uniform data of amplitude xmax has coefficients near xmax Delta / sqrt(S)
+times a few), and the call is redone with per-ciphertext scale-down exponents (kernels.hip
+launch_encrypt_approx); CKKS.encode_redo_count() says whether it was.  Every ciphertext is bit-exact vs
+the oracle's restatement (or_encode_coeffs_ex), and decrypts within 2^-40 relative of the input.
+tests/test_gpu_encode_edge.py walks the range's edges on every dispatch branch.
 
 Tolerances: a fresh ciphertext decrypts within 2^-40 * max|x|, because the scale-down keeps 62 bits
 of every coefficient.  An aggregate decrypts within 2^-38 * max|x|.  Weighted sums beyond the
@@ -37,17 +40,41 @@ def _arrays(ck):
             inf["batch"], inf["delta"])
 
 
-# 2^9.5: |x Delta| between 2^61 and 2^62 (the redo with logApprox = 0); from 2^10 on, logApprox > 0
-@pytest.mark.parametrize("xmax", [2.0 ** 9.5, 2.0 ** 10, 2.0 ** 14, 2.0 ** 20, 1e12])
+def _redone(x, N, S, delta):
+    """Whether a call encrypting x is redone, and why, from the oracle's encode: (some logApprox > 0,
+    the largest |coefficient| over the ciphertexts whose logApprox is 0)."""
+    las, top = [], 0
+    for k in range(0, len(x), S):
+        c, la = O.encode_coeffs_ex(x[k:k + S], N, S, delta)
+        las.append(la)
+        if la == 0:
+            top = max(top, int(np.abs(c).max()))
+    return max(las) > 0, top
+
+
+# What these inputs reach at 2^15 / L4 (max coefficient, exponent; O.encode_coeffs_ex): 2^9.5 -> 2^55.4,
+# 2^10 -> 2^55.7, 2^14 -> 2^59.8: all on the fast path, never flagged; 2^16 -> 2^61.8 with logApprox 0
+# (the redo that scales nothing down); 2^20 -> logApprox 4; 1e12 -> logApprox 24
+REDONE = {2.0 ** 9.5: 0, 2.0 ** 10: 0, 2.0 ** 14: 0, 2.0 ** 16: 1, 2.0 ** 20: 1, 1e12: 1}
+
+
+@pytest.mark.parametrize("xmax", list(REDONE))
 def test_large_values_bitexact_and_decrypt(c2, xmax):
     q, psi, N, S, delta = _arrays(c2)
+    redo = REDONE[xmax]
     pk, sk = c2.get_keys()
     rng = np.random.default_rng(int(np.log2(xmax) * 10))
     x = rng.uniform(-xmax, xmax, 3 * S - 11)
     x[S + 7] = xmax
+    scaled, top = _redone(x, N, S, delta)
+    assert redo == (scaled or top > 2 ** 61)
+    if xmax == 2.0 ** 16:
+        assert not scaled and top > 2 ** 61
     seed = 900 + int(np.log2(xmax))
     c2.set_seed(seed)
+    n0 = c2.encode_redo_count()
     blob = c2.encrypt(x)
+    assert c2.encode_redo_count() - n0 == redo
     got = m.blob_residues(blob, N, len(q))
     ref = O.encrypt_vector(x, pk, q, psi, N, S, delta, seed=seed, g0=0)
     assert np.array_equal(got, ref)
@@ -64,34 +91,64 @@ def test_only_some_ciphertexts_scale_down(c2):
     x = np.random.default_rng(3).uniform(-1, 1, 3 * S)
     x[S:2 * S] *= 2.0 ** 18
     c2.set_seed(31)
+    n0 = c2.encode_redo_count()
     got = m.blob_residues(c2.encrypt(x), N, len(q))
+    assert c2.encode_redo_count() - n0 == 1
     ref = O.encrypt_vector(x, pk, q, psi, N, S, delta, seed=31, g0=0)
     assert np.array_equal(got, ref)
     small = x.copy()
     small[S:2 * S] = 0.5
     c2.set_seed(31)
     fast = m.blob_residues(c2.encrypt(small), N, len(q))
+    assert c2.encode_redo_count() - n0 == 1  # the fast path
     assert np.array_equal(got[0], fast[0]) and np.array_equal(got[2], fast[2])
 
 
 def test_device_api_and_multichunk_bytes_api(c2):
-    """D.encrypt (device-resident) and a 70-ciphertext bytes-API call (3 pipeline chunks, large
-    values in the middle chunk only: the whole call is redone) are bit-exact vs the oracle."""
+    """D.encrypt (device-resident) and a 70-ciphertext bytes-API call (3 pipeline chunks) are bit-exact
+    vs the oracle.  The device call's third ciphertext has coefficients up to 2^61.9 with logApprox 0:
+    redone, once.  The bytes call's one slot of 3e6 spreads to coefficients of 2^59.5 only: the fast
+    path, no redo (the chunked redo is test_chunked_bytes_call_is_redone_once)."""
     q, psi, N, S, delta = _arrays(c2)
     pk, _ = c2.get_keys()
     x = np.random.default_rng(4).uniform(-1, 1, 4 * S)
     x[2 * S:3 * S] *= 2.0 ** 16
     c2.set_seed(41)
+    n0 = c2.encode_redo_count()
     ct = D.encrypt(c2, torch.from_numpy(x).cuda())
     torch.cuda.synchronize()
+    assert c2.encode_redo_count() - n0 == 1
     assert np.array_equal(ct.cpu().numpy().view(np.uint64), O.encrypt_vector(x, pk, q, psi, N, S, delta, seed=41))
     K = 70
     xb = np.random.default_rng(5).uniform(-1, 1, K * S - 3)
     xb[40 * S + 17] = 3.0e6
     c2.set_seed(42)
     got = m.blob_residues(c2.encrypt(xb), N, len(q))
+    assert c2.encode_redo_count() - n0 == 1
     for k in (0, 39, 40, 41, 69):
         ref = O.encrypt_vector(xb[k * S:(k + 1) * S], pk, q, psi, N, S, delta, seed=42, g0=k)
+        assert np.array_equal(got[k], ref[0]), k
+
+
+def test_chunked_bytes_call_is_redone_once(c2):
+    """70 ciphertexts through the bytes API (3 pipeline chunks of 32) with flagged ciphertexts in the
+    second and third chunks: the whole call is redone, and counted once."""
+    q, psi, N, S, delta = _arrays(c2)
+    pk, _ = c2.get_keys()
+    K = 70
+    xb = np.random.default_rng(8).uniform(-1, 1, K * S - 3)
+    xb[40 * S + 17] = 3.0e8  # logApprox 5
+    xb[41 * S:42 * S] *= 2.0 ** 16  # coefficients above 2^61, logApprox 0
+    xb[69 * S + 5] = -1e12  # logApprox 16
+    las = [O.encode_coeffs_ex(xb[k * S:(k + 1) * S], N, S, delta)[1] for k in (39, 40, 41, 69)]
+    assert las[0] == 0 and las[1] > 0 and las[2] == 0 and las[3] > las[1]
+    assert _redone(xb[41 * S:42 * S], N, S, delta)[1] > 2 ** 61
+    c2.set_seed(43)
+    n0 = c2.encode_redo_count()
+    got = m.blob_residues(c2.encrypt(xb), N, len(q))
+    assert c2.encode_redo_count() - n0 == 1
+    for k in (0, 39, 40, 41, 42, 69):
+        ref = O.encrypt_vector(xb[k * S:(k + 1) * S], pk, q, psi, N, S, delta, seed=43, g0=k)
         assert np.array_equal(got[k], ref[0]), k
 
 
@@ -104,7 +161,9 @@ def test_aggregate_of_large_values(c2):
     xs = [rng.uniform(-2.0 ** 20, 2.0 ** 20, 2 * S) for _ in range(3)]
     w = [0.2, 0.3, 0.5]
     c2.set_seed(51)
+    n0 = c2.encode_redo_count()
     blobs = [c2.encrypt(x) for x in xs]
+    assert c2.encode_redo_count() - n0 == 3
     res = [m.blob_residues(b, N, len(q)) for b in blobs]
     agg = c2.computeWeightedAverage(blobs, w)
     ar = m.blob_residues(agg, N, len(q))
@@ -126,10 +185,14 @@ def test_reference_keys_and_refusals():
     for fmt in ("palisade", "shelfi", "packed"):
         ck.set_wire_format(fmt)
         ck.set_seed(62)
+        n0 = ck.encode_redo_count()
         b = ck.encrypt(x)
+        assert ck.encode_redo_count() - n0 == 1
         assert np.array_equal(m.blob_residues(b, N, len(q), ckks=ck),
                               O.encrypt_vector(x, pk, q, psi, N, S, delta, seed=62))
         assert np.abs(ck.decrypt(b, 4) - x).max() <= 2.0 ** -40 * 1e9
+    n0 = ck.encode_redo_count()
     for bad in (np.nan, np.inf, -np.inf):
         with pytest.raises(ValueError, match="non-finite"):
             ck.encrypt(np.array([1e9, bad]))
+    assert ck.encode_redo_count() == n0  # a refusal is not a redo

@@ -29,8 +29,10 @@ import SHELFI_FHE as m  # noqa: E402
 
 SHAPES = [
     # (batch, ringDim, multDepth, scaleBits, firstModBits)
-    (1024, 0, 1, 52, 60),      # N = 2^11
-    (2048, 0, 1, 52, 60),      # N = 2^12
+    (1024, 0, 1, 52, 60),      # ringDim 0 is ParamsGen's choice: N = 2^13 for these two batches (gap 4 and 2),
+    (2048, 0, 1, 52, 60),      # as the assertion on ring_dim below records
+    (1024, 2048, 1, 52, 60),   # N = 2^11
+    (2048, 4096, 1, 52, 60),   # N = 2^12
     (8192, 0, 2, 52, 60),      # N = 2^14, L = 3
     (8192, 32768, 3, 52, 60),  # N = 2^15, gap 2
     (4096, 32768, 3, 52, 60),  # N = 2^15, gap 4
@@ -52,6 +54,7 @@ def test_encrypt_decrypt_ntt_bitexact(batch, ring, depth, sb, fb, tmp_path):
     q = np.array(inf["moduli"], np.uint64)
     psi = np.array(inf["roots"], np.uint64)
     N, S, delta = inf["ring_dim"], inf["batch"], inf["delta"]
+    assert N == (ring or {1024: 8192, 2048: 8192, 8192: 16384, 32768: 65536, 65536: 131072, 4096: 8192}[batch])
     n = S + S // 3  # two ciphertexts, the second partial
     x = np.random.default_rng(batch + depth).uniform(-1, 1, n).astype(np.float32).astype(np.float64)
     seed = 77
