@@ -59,6 +59,45 @@ def pack_arena(cts, q, N):
     return np.concatenate(out)
 
 
+def pack_one(ct, q, N):
+    """pack_arena([ct], q, N) for one learner (the packed wire payload, C = 1), vectorised over
+    rows and lanes: tests that need many packed blobs use it; test_wavg_cases.py pins it to
+    pack_arena."""
+    K, _, L, _ = ct.shape
+    U = widths(q)
+    nch = N // 512
+    out = []
+    for k in range(K):
+        for p in range(2):
+            for t in range(L):
+                Bt, F, D, N4, H2, H1, O2, O1 = _geom(U[t])
+                # [chunk][j >> 1][lane][j & 1] -> x[chunk][lane][j]
+                x = ct[k, p, t].astype(np.uint64).reshape(nch, 4, 64, 2).transpose(0, 2, 1, 3).reshape(nch, 64, 8)
+                w = np.zeros((nch, 64, D + 2), np.uint64)
+                fl = np.zeros((nch, 64), np.uint64)
+                lo32 = np.uint64(0xFFFFFFFF)
+                for j in range(8):
+                    v = x[:, :, j] & np.uint64((1 << Bt) - 1)
+                    fl |= ((x[:, :, j] >> np.uint64(Bt)) & np.uint64(1)) << np.uint64(j)
+                    i, sh = (j * Bt) >> 5, (j * Bt) & 31
+                    w[:, :, i] |= (v << np.uint64(sh)) & lo32
+                    w[:, :, i + 1] |= (v >> np.uint64(32 - sh)) & lo32
+                    if sh + Bt > 64:
+                        w[:, :, i + 2] |= v >> np.uint64(64 - sh)
+                w = w[:, :, :D].astype(np.uint32)
+                sl = np.zeros((nch, 16 * U[t]), np.uint32)
+                for pl in range(N4):
+                    sl[:, pl * 256:(pl + 1) * 256] = w[:, :, 4 * pl:4 * pl + 4].reshape(nch, 256)
+                if H2:
+                    sl[:, O2:O2 + 128] = w[:, :, 4 * N4:4 * N4 + 2].reshape(nch, 128)
+                if H1:
+                    sl[:, O1:O1 + 64] = w[:, :, D - 1]
+                if F:
+                    sl.view(np.uint8)[:, 64 * Bt:64 * Bt + 64] = fl.astype(np.uint8)
+                out.append(sl.reshape(-1))
+    return np.concatenate(out)
+
+
 def unpack_arena(words, C, K, L, N, q):
     """Inverse of pack_arena: C [K][2][L][N] uint64 batches."""
     U = widths(q)

@@ -176,9 +176,12 @@ def test_wavg_arena_bitexact(cfg2, C, K):
     (30, 45, 1, 5, 2),    # 45 bits (flag plane) and 30-bit towers at the 32-bit minimum
 ])
 def test_wavg_arena_packed_widths(tmp_path, monkeypatch, scale, first, depth, C, K):
-    """The packed arena at every width class its kernels carry: residues at 0, q-1
-    (the top bit, for towers whose bitlength is 1 mod 4, lives in the flag plane) and random, device and host placement, whole-range and sub-range aggregation == oracle, at
-    every learner unroll depth of wavg_packed and under its probe switches."""
+    """The packed arena at the width classes 32, 36, 40, 41, 44, 45, 48, 53, 57 and 60
+    (the other classes, every class at its accumulators' limits and the learner-group edges are
+    tests/test_gpu_wavg_limits.py): residues at 0, q-1 (the top bit, for towers whose bitlength is
+    1 mod 4, lives in the flag plane) and random, device and host placement, whole-range and
+    sub-range aggregation == oracle, at every learner unroll depth of wavg_packed and under its
+    probe switches."""
     ck = m.CKKS("ckks", 1024, scale, str(tmp_path) + os.sep, multDepth=depth, firstModBits=first,
                 seed=3, decodeNoise=False)
     assert ck.genCryptoContextAndKeyGen() == 1
