@@ -351,6 +351,45 @@ class CKKS(Scheme):
             raise ValueError("evaluation key must be [2][dnum][L + kP][N]")
         check(self._lib.shelfi_set_eval_key(self._ctx, evk.ctypes.data_as(_lib.u64p)), "set_eval_key")
 
+    # ------------------------------- slot rotations / EvalSum (mkhe.cpp:124, :274, :372) --
+    def rotationKeyGen(self, indices: Iterable[int]) -> None:
+        """cc->EvalAtIndexKeyGen(sk, indices): adds the rotation keys of `indices` (|r| < batch;
+        0 is skipped) to those held, generated on the device in a stream domain of their own.  A
+        context holds at most 64; a key reload or regeneration drops them."""
+        idx = np.ascontiguousarray(list(indices), dtype=np.int32)
+        check(self._lib.shelfi_rotation_keygen(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size),
+              "rotationKeyGen")
+
+    def evalSumKeyGen(self) -> None:
+        """cc->EvalSumKeyGen(sk): the rotation keys of indices 1, 2, 4, ..., batch / 2."""
+        check(self._lib.shelfi_eval_sum_keygen(self._ctx), "evalSumKeyGen")
+
+    def rotation_key_indices(self) -> List[int]:
+        """The rotation indices whose keys this context holds."""
+        n = C.c_size_t()
+        check(self._lib.shelfi_rotation_key_indices(self._ctx, None, 0, C.byref(n)), "rotation_key_indices")
+        out = (C.c_int32 * max(1, n.value))()
+        check(self._lib.shelfi_rotation_key_indices(self._ctx, out, n.value, C.byref(n)), "rotation_key_indices")
+        return [int(out[i]) for i in range(n.value)]
+
+    def _rotation_key_shape(self):
+        inf, ek = self.info(), self.eval_key_info()
+        return (2, ek["dnum"], inf["num_towers"] + len(ek["special_moduli"]), inf["ring_dim"])
+
+    def get_rotation_key(self, r: int) -> np.ndarray:
+        """The rotation key of index r, [2][dnum][L + kP][N] like the evaluation key."""
+        out = np.zeros(self._rotation_key_shape(), np.uint64)
+        check(self._lib.shelfi_get_rotation_key(self._ctx, int(r), out.ctypes.data_as(_lib.u64p)),
+              "get_rotation_key")
+        return out
+
+    def set_rotation_key(self, r: int, key: np.ndarray) -> None:
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        if key.size != self._lib.shelfi_eval_key_words(self._ctx):
+            raise ValueError("rotation key must be [2][dnum][L + kP][N]")
+        check(self._lib.shelfi_set_rotation_key(self._ctx, int(r), key.ctypes.data_as(_lib.u64p)),
+              "set_rotation_key")
+
     # ------------------------------------------------------------ hot path --
     def _take(self, ptr: "_lib.u8p", n: int) -> bytes:
         try:
@@ -424,6 +463,14 @@ def params_generate(batchSize: int = 4096, scaleFactorBits: int = 52, multDepth:
     check(lib.shelfi_params_generate(ringDim, L, scaleFactorBits, firstModBits, batchSize,
                                      C.byref(N), q, psi), "params_generate")
     return int(N.value), [int(x) for x in q], [int(x) for x in psi]
+
+
+def galois_element(ringDim: int, r: int) -> int:
+    """The Galois element of rotation index r on a ring of dimension ringDim: 5^r mod 2N, the
+    inverse for r < 0 (PALISADE's FindAutomorphismIndex2nComplex).  Host-only; |r| < ringDim / 2."""
+    g = C.c_uint32()
+    check(_lib.load().shelfi_galois_element(int(ringDim), int(r), C.byref(g)), "galois_element")
+    return g.value
 
 
 def special_primes(ringDim: int, moduli) -> dict:

@@ -180,6 +180,20 @@ SIGNATURES = {
     "shelfi_palisade_evalkey_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, u64p]),
     "shelfi_palisade_evalkey_rewrite": (C.c_int, [C.c_char_p, C.c_size_t, u64p, C.POINTER(u8p),
                                                   C.POINTER(C.c_size_t)]),
+    # slot rotations and EvalSum (mkhe.cpp:124, :274, :372; eval.cpp, rotate.hip)
+    "shelfi_galois_element": (C.c_int, [C.c_uint32, C.c_int32, C.POINTER(C.c_uint32)]),
+    "shelfi_rotation_keygen": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t]),
+    "shelfi_eval_sum_keygen": (C.c_int, [C.c_void_p]),
+    "shelfi_rotation_key_indices": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t,
+                                              C.POINTER(C.c_size_t)]),
+    "shelfi_get_rotation_key": (C.c_int, [C.c_void_p, C.c_int32, u64p]),
+    "shelfi_set_rotation_key": (C.c_int, [C.c_void_p, C.c_int32, u64p]),
+    "shelfi_dev_rotate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int32, C.c_void_p,
+                                    C.c_void_p]),
+    "shelfi_dev_eval_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
+                                      C.c_void_p]),
+    "shelfi_dev_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                 C.c_void_p]),
     # threshold CKKS (mkhe.cpp RunCKKS): key chain, partial decryption, fusion (threshold.hip)
     "shelfi_multiparty_keygen": (C.c_int, [C.c_void_p, u64p]),
     "shelfi_set_threshold_noise": (C.c_int, [C.c_void_p, C.c_double]),

@@ -498,6 +498,55 @@ def rescale(ckks, ct, out=None):
     return out
 
 
+def _like(ckks, ct, out):
+    """out (or a new tensor) shaped like the ciphertext batch ct, on its device."""
+    if out is None:
+        return _torch().empty_like(ct)
+    _check_ct(out, ckks, ct.shape[0], any_level=True)
+    if out.shape != ct.shape or out.device != ct.device:
+        raise ValueError("out must be a contiguous tensor shaped like the input, on its device")
+    return out
+
+
+def rotate(ckks, ct, r: int, out=None):
+    """cc->EvalAtIndex(ct, r) for K ciphertexts of any level: slot i of the result holds slot
+    (i + r) mod batch of the input (r > 0 rotates left).  Needs ckks.rotationKeyGen([r]) (or any index
+    with the same Galois element); r = 0 is a copy.  out must not overlap ct.  Scale unchanged."""
+    _check_ct(ct, ckks, any_level=True)
+    out = _like(ckks, ct, out)
+    check(_lib.load().shelfi_dev_rotate(ckks._ctx, C.c_void_p(ct.data_ptr()), ct.shape[0], int(ct.shape[2]), int(r),
+                                        C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(ct))), "dev_rotate")
+    return out
+
+
+def eval_sum(ckks, ct, n: int, out=None):
+    """cc->EvalSum(ct, n), n a power of two in 1..batch: slot i of the result holds
+    sum_{j < n} x[(i + j) mod batch], by log2(n) rotate-and-add steps (needs the keys of indices
+    1, 2, .., n / 2: ckks.evalSumKeyGen()).  out must not overlap ct.  Scale unchanged."""
+    _check_ct(ct, ckks, any_level=True)
+    out = _like(ckks, ct, out)
+    if n < 0 or n >= 1 << 32:
+        raise ValueError("EvalSum needs a power of two in 1..batch")
+    check(_lib.load().shelfi_dev_eval_sum(ckks._ctx, C.c_void_p(ct.data_ptr()), ct.shape[0], int(ct.shape[2]),
+                                          int(n), C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(ct))),
+          "dev_eval_sum")
+    return out
+
+
+def add(ckks, a, b, out=None):
+    """cc->EvalAdd(a, b) for K ciphertext pairs of the same level and scale: out = a + b mod q_t
+    (out may be a or b).  Needs no keys; enqueued on a's stream."""
+    _check_ct(a, ckks, any_level=True)
+    _check_ct(b, ckks, a.shape[0], any_level=True)
+    if a.shape != b.shape or b.device != a.device:
+        raise ValueError("EvalAdd operands must have the same shape (same level) and device")
+    out = _like(ckks, a, out)
+    check(_lib.load().shelfi_dev_add(ckks._ctx, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), a.shape[0],
+                                     int(a.shape[2]), C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(a))),
+          "dev_add")
+    return out
+
+
 def ntt(ckks, polys, inverse: bool = False):
     """In-place negacyclic NTT (PALISADE order) of [P][N] polys; tower = p % L."""
     inf = ckks.info()

@@ -557,6 +557,40 @@ __device__ __forceinline__ void ntt_inv_block_stages(uint64_t* sm, uint32_t blkL
   }
 }
 
+// The key switch's first INTT pass (keyswitch.hip's tensor pass, rotate.hip's automorphism pass):
+// the block of the polynomial to switch sits in LDS in EVALUATION; its inverse stages run there and
+// the block goes to d2c -- lazy in [0, 4q) for the columns pass, or, for a single-block ring, the
+// scaled canonical coefficients.
+__device__ __forceinline__ void ks_intt_block_out(uint64_t* sm, uint32_t blkLog, uint32_t b, uint32_t logN,
+                                                  const uint64_t* __restrict__ itw,
+                                                  const uint64_t* __restrict__ itwp, const TowerConst& c,
+                                                  uint64_t* __restrict__ d2c_blk) {
+  const uint32_t blk = 1u << blkLog;
+  const uint64_t q = c.q;
+  ntt_inv_block_stages(sm, blkLog, b, logN, itw, itwp, q);
+  ulonglong2* D = reinterpret_cast<ulonglong2*>(d2c_blk);
+  if (logN == blkLog) {
+    for (uint32_t p = threadIdx.x; p < blk / 2; p += 256) {
+      const ulonglong2 v = lds_get2(sm, p);
+      D[p] = make_ulonglong2(canon4(shoup_lazy(v.x, c.ninv, c.ninv_shoup, q), q),
+                             canon4(shoup_lazy(v.y, c.ninv, c.ninv_shoup, q), q));
+    }
+  } else {  // lazy values in [0, 4q): the columns pass canonicalises
+    for (uint32_t p = threadIdx.x; p < blk / 2; p += 256) D[p] = lds_get2(sm, p);
+  }
+}
+
+// The automorphism sigma_g: X -> X^g (g odd) on a polynomial in EVALUATION, in the NTT's own
+// (bit-reversed) order: out[j] = in[galois_src(j)], where position j holds the value at
+// psi^(2 brev(j) + 1) and sigma_g(a)(psi^e) = a(psi^(g e)).  Aligned runs of 2^k positions map onto
+// aligned runs of 2^k positions (the low k bits of j are the high k bits of the exponent, which g
+// permutes among themselves), so galois_src(j ^ 1) = galois_src(j) ^ 1.
+__device__ __forceinline__ uint32_t galois_src(uint32_t j, uint32_t g, uint32_t logN) {
+  const uint32_t e = 2u * (__brev(j) >> (32 - logN)) + 1u;
+  const uint32_t ge = (g * e) & ((2u << logN) - 1u);  // g e mod 2N (the product may wrap: low bits only)
+  return __brev(ge >> 1) >> (32 - logN);
+}
+
 // Orders one wave's LDS writes before its own later LDS reads (no other wave involved): the DS
 // instructions of a wave execute in order, so a wavefront-scope fence (the compiler's ordering and
 // the lgkm wait) stands in for a workgroup barrier when every element a wave reads next was written

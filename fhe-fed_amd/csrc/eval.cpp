@@ -1,5 +1,7 @@
 // eval.cpp — C ABI of SURVEY §8 f4: EvalMultKeyGen, EvalMult (ct x ct) with HYBRID
-// relinearization, ModReduce, and the per-level tables they (and decrypt at a level) use.
+// relinearization, ModReduce, and the per-level tables they (and decrypt at a level) use; and of
+// the slot rotations built on the same key switch (mkhe.cpp:124, :274, :372):
+// rotation keys, Rotate, EvalSum and the plain EvalAdd (rotate.hip).
 //
 // None of this is on the reference's aggregation path (ckks.cpp:26 fixes multDepth = 1 and
 // computeWeightedAverage only multiplies by constants); it is the general-circuit part of
@@ -36,8 +38,18 @@ struct EvalState {
   uint64_t* evk = nullptr;     // [2][dnum][L + kP][N] (b-vector, a-vector)
   uint64_t* evk_sh = nullptr;  // Shoup companions
   std::vector<uint64_t> evk_host;
+  // rotation keys sigma_g(s) -> s in the evaluation key's layout, keyed by the Galois element g
+  struct RotKey {
+    uint32_t g = 0;
+    int32_t index = 0;  // the index it was first asked for under
+    uint64_t* key = nullptr;
+    uint64_t* key_sh = nullptr;
+    std::vector<uint64_t> host;
+  };
+  std::vector<RotKey> rot;
   LevelState lv[kMaxTowers + 1];  // index = towers Ll
 };
+constexpr size_t kMaxRotKeys = 64;
 
 static uint64_t mm(uint64_t a, uint64_t b, uint64_t q) { return (uint64_t)(((u128)a * b) % q); }
 
@@ -64,6 +76,11 @@ void eval_release(shelfi_ctx* ctx, bool keys_only) {
   dfree_t(ev->evk);
   dfree_t(ev->evk_sh);
   ev->evk_host.clear();
+  for (auto& r : ev->rot) {  // rotation keys belong to the secret key too
+    dfree_t(r.key);
+    dfree_t(r.key_sh);
+  }
+  ev->rot.clear();
   if (keys_only) return;
   for (auto& l : ev->lv) free_level(l);
   delete ev;
@@ -229,7 +246,9 @@ static LevelState& level(shelfi_ctx* ctx, uint32_t Ll) {
 // tables of Q_l for decrypt at a level (call_state.cpp decode_pass): the Q_l tables alone
 const DeviceTables& level_tables(shelfi_ctx* ctx, uint32_t Ll) { return level_q(ctx, Ll); }
 
-static void install_evk(shelfi_ctx* ctx, EvalState& ev, const uint64_t* evk) {
+// Shoup companions of a key in the evaluation key's layout, [2][dnum][L + kP][N]; a residue >= its
+// modulus is refused (`what` names the key)
+static std::vector<uint64_t> key_shoup(shelfi_ctx* ctx, EvalState& ev, const uint64_t* evk, const char* what) {
   const Params& p = ctx->p;
   if (!ev.ks_error.empty()) throw Error{SHELFI_ERR_ARG, ev.ks_error};
   const uint32_t T0 = p.L + ev.kP;
@@ -238,14 +257,83 @@ static void install_evk(shelfi_ctx* ctx, EvalState& ev, const uint64_t* evk) {
   for (size_t i = 0; i < words; ++i) {
     const uint32_t t = (uint32_t)((i % TN) / p.N);
     const uint64_t q = t < p.L ? p.q[t] : ev.p[t - p.L];
-    if (evk[i] >= q) throw Error{SHELFI_ERR_FORMAT, "evaluation key residue >= modulus"};
+    if (evk[i] >= q) throw Error{SHELFI_ERR_FORMAT, std::string(what) + " residue >= modulus"};
     sh[i] = shoup(evk[i], q);
   }
+  return sh;
+}
+
+static void install_evk(shelfi_ctx* ctx, EvalState& ev, const uint64_t* evk) {
+  const std::vector<uint64_t> sh = key_shoup(ctx, ev, evk, "evaluation key");
+  const size_t words = sh.size();
   dfree_t(ev.evk);
   dfree_t(ev.evk_sh);
   ev.evk_host.assign(evk, evk + words);
   ev.evk = upload(evk, words);
   ev.evk_sh = upload(sh.data(), words);
+}
+
+// g = 5^index mod 2N, the inverse for a negative index (PALISADE's FindAutomorphismIndex2nComplex)
+static uint32_t galois_element(uint32_t N, int32_t index) {
+  const uint64_t M = 2ull * N;
+  const uint64_t n = index < 0 ? (uint64_t)(-(int64_t)index) : (uint64_t)index;
+  uint64_t g = 1;
+  for (uint64_t i = 0; i < n; ++i) g = g * 5 % M;
+  if (index < 0) {  // g^-1 mod 2^k = g^(2^(k-2) - 1): the odd residues' exponent divides N / 2
+    uint64_t inv = 1, b = g;
+    for (uint64_t e = N / 2 - 1; e; e >>= 1, b = b * b % M)
+      if (e & 1) inv = inv * b % M;
+    g = inv;
+  }
+  return (uint32_t)g;
+}
+
+static uint32_t rotation_galois(const shelfi_ctx* ctx, int32_t index) {
+  const int64_t batch = ctx->p.batch;
+  if (index <= -batch || index >= batch) throw Error{SHELFI_ERR_ARG, "rotation index must be below the batch size"};
+  return galois_element(ctx->p.N, index);
+}
+
+static EvalState::RotKey* find_rot(EvalState* ev, uint32_t g) {
+  if (ev)
+    for (auto& r : ev->rot)
+      if (r.g == g) return &r;
+  return nullptr;
+}
+
+static const EvalState::RotKey& require_rot(shelfi_ctx* ctx, int32_t index, uint32_t g) {
+  const EvalState::RotKey* r = find_rot(ctx->ev, g);
+  if (!r)
+    throw Error{SHELFI_ERR_STATE, "no rotation key for index " + std::to_string(index) +
+                                      ": call rotationKeyGen() / evalSumKeyGen() first"};
+  return *r;
+}
+
+static void install_rot(shelfi_ctx* ctx, EvalState& ev, int32_t index, uint32_t g, const uint64_t* key) {
+  const std::vector<uint64_t> sh = key_shoup(ctx, ev, key, "rotation key");
+  const size_t words = sh.size();
+  EvalState::RotKey* r = find_rot(&ev, g);
+  if (!r) {
+    if (ev.rot.size() >= kMaxRotKeys) throw Error{SHELFI_ERR_ARG, "a context holds at most 64 rotation keys"};
+    ev.rot.emplace_back();
+    r = &ev.rot.back();
+    r->g = g;
+    r->index = index;
+  }
+  uint64_t *kd = nullptr, *ks = nullptr;
+  try {
+    kd = upload(key, words);
+    ks = upload(sh.data(), words);
+  } catch (...) {
+    dfree_t(kd);
+    if (!r->key) ev.rot.pop_back();  // a new entry that never got its key
+    throw;
+  }
+  dfree_t(r->key);
+  dfree_t(r->key_sh);
+  r->key = kd;
+  r->key_sh = ks;
+  r->host.assign(key, key + words);
 }
 
 // key-eval-mult.txt metadata of this context's evaluation key (PALISADE keys required: the
@@ -365,50 +453,129 @@ size_t shelfi_eval_key_words(const shelfi_ctx* ctx) {
   return 2ull * dn * (ctx->p.L + kP) * ctx->p.N;
 }
 
+}  // extern "C"
+
+namespace shelfi {
+// A key-switching key s' -> s on the device, read back: galois = 0: s' = s^2 (EvalMultKeyGen);
+// galois = g: s' = sigma_g(s) (a rotation key).  ctx lock held, device set.
+static std::vector<uint64_t> switch_keygen(shelfi_ctx* ctx, uint32_t galois) {
+  require_keys(ctx);
+  const Params& p = ctx->p;
+  EvalState& ev = eval_state(ctx);
+  LevelState& l = level(ctx, p.L);
+  EvkGenConst gc{};
+  gc.q0 = p.q[0];
+  for (uint32_t t = 0; t < p.L; ++t) {
+    gc.pmod[t] = 1;
+    for (uint32_t m = 0; m < ev.kP; ++m) gc.pmod[t] = mm(gc.pmod[t], ev.p[m] % p.q[t], p.q[t]);
+  }
+  gc.L = p.L;
+  gc.kP = ev.kP;
+  gc.dnum = ev.dnum;
+  gc.alpha = ev.alpha;
+  gc.logN = p.logN;
+  uint32_t key[8];
+  if (ctx->seed)
+    seed_to_key(ctx->seed, key);
+  else
+    os_random(key, 32);
+  const size_t words = 2ull * ev.dnum * (p.L + ev.kP) * p.N;
+  void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, evk_scratch_bytes(p.L, ev.kP, p.N));
+  uint64_t* evk_d = nullptr;
+  SHELFI_HIP(hipMalloc((void**)&evk_d, words * 8));
+  std::vector<uint64_t> host(words);
+  try {
+    launch_evk_keygen(gc, ctx->dt, l.ext, ctx->dt.cdt, ctx->dt.cdt_len, key, ctx->dk.sk, evk_d, scratch,
+                      ctx->stream, galois);
+    SHELFI_HIP(hipMemcpyAsync(host.data(), evk_d, words * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SHELFI_HIP(hipStreamSynchronize(ctx->stream));
+  } catch (...) {
+    (void)hipFree(evk_d);
+    throw;
+  }
+  (void)hipFree(evk_d);
+  std::memset(key, 0, sizeof(key));
+  return host;
+}
+
+static void rotation_keygen(shelfi_ctx* ctx, const int32_t* indices, size_t n) {
+  require_keys(ctx);
+  DeviceGuard dg(ctx->device);
+  EvalState& ev = eval_state(ctx);
+  std::vector<uint32_t> gs(n);
+  size_t fresh = 0;  // refuse a list that would not fit before generating any of it
+  for (size_t i = 0; i < n; ++i) {
+    gs[i] = indices[i] ? rotation_galois(ctx, indices[i]) : 0;
+    if (gs[i] && !find_rot(&ev, gs[i]) && std::find(gs.begin(), gs.begin() + i, gs[i]) == gs.begin() + i) ++fresh;
+  }
+  if (ev.rot.size() + fresh > kMaxRotKeys) throw Error{SHELFI_ERR_ARG, "a context holds at most 64 rotation keys"};
+  for (size_t i = 0; i < n; ++i)
+    if (gs[i]) install_rot(ctx, ev, indices[i], gs[i], switch_keygen(ctx, gs[i]).data());
+}
+}  // namespace shelfi
+
+extern "C" {
+
 int shelfi_eval_mult_keygen(shelfi_ctx* ctx) {
   if (!ctx) return SHELFI_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   return guarded([&] {
-    require_keys(ctx);
     DeviceGuard g(ctx->device);
-    const Params& p = ctx->p;
-    EvalState& ev = eval_state(ctx);
-    LevelState& l = level(ctx, p.L);
-    EvkGenConst gc{};
-    gc.q0 = p.q[0];
-    uint64_t P[kMaxTowers];
-    for (uint32_t t = 0; t < p.L; ++t) {
-      P[t] = 1;
-      for (uint32_t m = 0; m < ev.kP; ++m) P[t] = mm(P[t], ev.p[m] % p.q[t], p.q[t]);
-      gc.pmod[t] = P[t];
-    }
-    gc.L = p.L;
-    gc.kP = ev.kP;
-    gc.dnum = ev.dnum;
-    gc.alpha = ev.alpha;
-    gc.logN = p.logN;
-    uint32_t key[8];
-    if (ctx->seed)
-      seed_to_key(ctx->seed, key);
-    else
-      os_random(key, 32);
-    const size_t words = 2ull * ev.dnum * (p.L + ev.kP) * p.N;
-    void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, evk_scratch_bytes(p.L, ev.kP, p.N));
-    uint64_t* evk_d = nullptr;
-    SHELFI_HIP(hipMalloc((void**)&evk_d, words * 8));
-    std::vector<uint64_t> host(words);
-    try {
-      launch_evk_keygen(gc, ctx->dt, l.ext, ctx->dt.cdt, ctx->dt.cdt_len, key, ctx->dk.sk, evk_d, scratch,
-                        ctx->stream);
-      SHELFI_HIP(hipMemcpyAsync(host.data(), evk_d, words * 8, hipMemcpyDeviceToHost, ctx->stream));
-      SHELFI_HIP(hipStreamSynchronize(ctx->stream));
-    } catch (...) {
-      (void)hipFree(evk_d);
-      throw;
-    }
-    (void)hipFree(evk_d);
-    std::memset(key, 0, sizeof(key));
-    install_evk(ctx, ev, host.data());
+    const std::vector<uint64_t> host = switch_keygen(ctx, 0);
+    install_evk(ctx, eval_state(ctx), host.data());
+  });
+}
+
+int shelfi_galois_element(uint32_t ring_dim, int32_t index, uint32_t* g) {
+  if (!g || ring_dim < 4 || ring_dim > (1u << 17) || (ring_dim & (ring_dim - 1)) ||
+      index <= -(int64_t)(ring_dim / 2) || index >= (int64_t)(ring_dim / 2)) {
+    set_error("galois element: ring_dim a power of two in 4..2^17, |index| < ring_dim / 2");
+    return SHELFI_ERR_ARG;
+  }
+  *g = galois_element(ring_dim, index);
+  return SHELFI_OK;
+}
+
+int shelfi_rotation_keygen(shelfi_ctx* ctx, const int32_t* indices, size_t n) {
+  if (!ctx || (n && !indices)) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] { rotation_keygen(ctx, indices, n); });
+}
+
+int shelfi_eval_sum_keygen(shelfi_ctx* ctx) {
+  if (!ctx) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    std::vector<int32_t> idx;
+    for (uint32_t r = 1; r < ctx->p.batch; r <<= 1) idx.push_back((int32_t)r);
+    rotation_keygen(ctx, idx.data(), idx.size());
+  });
+}
+
+int shelfi_rotation_key_indices(const shelfi_ctx* ctx, int32_t* out, size_t cap, size_t* n) {
+  if (!ctx || !n || (cap && !out)) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  *n = ctx->ev ? ctx->ev->rot.size() : 0;
+  for (size_t i = 0; i < *n && i < cap; ++i) out[i] = ctx->ev->rot[i].index;
+  return SHELFI_OK;
+}
+
+int shelfi_get_rotation_key(const shelfi_ctx* ctx, int32_t index, uint64_t* key) {
+  if (!ctx || !key) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    const EvalState::RotKey& r = require_rot(const_cast<shelfi_ctx*>(ctx), index, rotation_galois(ctx, index));
+    std::memcpy(key, r.host.data(), r.host.size() * 8);
+  });
+}
+
+int shelfi_set_rotation_key(shelfi_ctx* ctx, int32_t index, const uint64_t* key) {
+  if (!ctx || !key) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    if (!index) throw Error{SHELFI_ERR_ARG, "rotation index 0 has no key"};
+    DeviceGuard g(ctx->device);
+    install_rot(ctx, eval_state(ctx), index, rotation_galois(ctx, index), key);
   });
 }
 
@@ -551,6 +718,111 @@ int shelfi_dev_rescale(shelfi_ctx* ctx, const uint64_t* in_dev, size_t K, uint32
                      out_dev + k0 * 2ull * (towers - 1) * p.N, scratch, s);
     }
     SHELFI_HIP(hipStreamSynchronize(s));
+  });
+}
+
+static bool overlaps(const uint64_t* a, const uint64_t* b, uint64_t words) {
+  return a < b + words && b < a + words;
+}
+
+int shelfi_dev_rotate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, int32_t index,
+                      uint64_t* out_dev, void* stream) {
+  if (!ctx || (K && (!ct_dev || !out_dev))) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    DeviceGuard dg(ctx->device);
+    const uint32_t N = ctx->p.N;
+    const uint32_t g = rotation_galois(ctx, index);
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t ctw = 2ull * towers * N;
+    if (!index) {  // the identity: a copy (out may be the input itself)
+      level_q(ctx, towers);
+      if (!K || out_dev == ct_dev) return;
+      if (overlaps(ct_dev, out_dev, ctw * K))
+        throw Error{SHELFI_ERR_ARG, "rotation input and output must not overlap"};
+      SHELFI_HIP(hipMemcpyAsync(out_dev, ct_dev, ctw * K * 8, hipMemcpyDeviceToDevice, s));
+      SHELFI_HIP(hipStreamSynchronize(s));
+      return;
+    }
+    LevelState& l = level(ctx, towers);
+    const EvalState::RotKey& rk = require_rot(ctx, index, g);
+    if (!K) return;
+    // the gather reads whole rows of the input while other workgroups write the output
+    if (overlaps(ct_dev, out_dev, ctw * K)) throw Error{SHELFI_ERR_ARG, "rotation input and output must not overlap"};
+    const KsArgs& a = l.args;
+    const uint64_t kc_max = chunk_of(K, ks_scratch_bytes(a.Ll, a.kP, a.dn, a.alpha, N, 1));
+    void* scratch =
+        ensure(ctx->scratch, ctx->scratch_bytes, ks_scratch_bytes(a.Ll, a.kP, a.dn, a.alpha, N, kc_max));
+    for (uint64_t k0 = 0; k0 < K; k0 += kc_max) {
+      const uint64_t kc = std::min<uint64_t>(kc_max, K - k0);
+      launch_rotate(a, ctx->dt, l.ext, l.dtf, rk.key, rk.key_sh, g, ct_dev + k0 * ctw, kc, out_dev + k0 * ctw,
+                    scratch, s);
+    }
+    SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
+  });
+}
+
+int shelfi_dev_eval_sum(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, uint32_t n,
+                        uint64_t* out_dev, void* stream) {
+  if (!ctx || (K && (!ct_dev || !out_dev))) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    DeviceGuard dg(ctx->device);
+    const uint32_t N = ctx->p.N;
+    if (!n || (n & (n - 1)) || n > ctx->p.batch)
+      throw Error{SHELFI_ERR_ARG, "EvalSum needs a power of two in 1..batch"};
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t ctw = 2ull * towers * N;
+    struct Step {
+      uint32_t g;
+      const EvalState::RotKey* rk;
+    };
+    std::vector<Step> steps;  // every key is looked up before anything is enqueued
+    level_q(ctx, towers);
+    for (uint32_t r = 1; r < n; r <<= 1) {
+      const uint32_t g = rotation_galois(ctx, (int32_t)r);
+      steps.push_back(Step{g, &require_rot(ctx, (int32_t)r, g)});
+    }
+    if (!K) return;
+    if (overlaps(ct_dev, out_dev, ctw * K)) throw Error{SHELFI_ERR_ARG, "EvalSum input and output must not overlap"};
+    SHELFI_HIP(hipMemcpyAsync(out_dev, ct_dev, ctw * K * 8, hipMemcpyDeviceToDevice, s));
+    if (!steps.empty()) {
+      LevelState& l = level(ctx, towers);
+      const KsArgs& a = l.args;
+      // per chunk: the key switch's scratch, then the rotated copy the accumulator takes in
+      const size_t per_ct = ks_scratch_bytes(a.Ll, a.kP, a.dn, a.alpha, N, 1) + ctw * 8;
+      const uint64_t kc_max = chunk_of(K, per_ct);
+      const size_t ks_bytes = (ks_scratch_bytes(a.Ll, a.kP, a.dn, a.alpha, N, kc_max) + 63) & ~(size_t)63;
+      void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, ks_bytes + kc_max * ctw * 8);
+      uint64_t* rot = reinterpret_cast<uint64_t*>(static_cast<char*>(scratch) + ks_bytes);
+      for (uint64_t k0 = 0; k0 < K; k0 += kc_max) {
+        const uint64_t kc = std::min<uint64_t>(kc_max, K - k0);
+        uint64_t* acc = out_dev + k0 * ctw;
+        for (const Step& st : steps) {
+          launch_rotate(a, ctx->dt, l.ext, l.dtf, st.rk->key, st.rk->key_sh, st.g, acc, kc, rot, scratch, s);
+          launch_ct_add(acc, rot, kc * 2 * towers, towers, ctx->p.logN, a.tq, acc, s);
+        }
+      }
+    }
+    SHELFI_HIP(hipStreamSynchronize(s));
+  });
+}
+
+int shelfi_dev_add(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev, size_t K, uint32_t towers,
+                   uint64_t* out_dev, void* stream) {
+  if (!ctx || (K && (!a_dev || !b_dev || !out_dev))) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    DeviceGuard dg(ctx->device);
+    const Params& p = ctx->p;
+    if (towers < 1 || towers > p.L) throw Error{SHELFI_ERR_ARG, "tower count out of range for this context"};
+    if (!K) return;
+    // each thread reads its residues before writing them: out may be an input exactly, not shifted
+    const uint64_t words = 2ull * towers * p.N * K;
+    for (const uint64_t* in : {a_dev, b_dev})
+      if (out_dev != in && overlaps(in, out_dev, words))
+        throw Error{SHELFI_ERR_ARG, "EvalAdd output must be an input exactly or not overlap the inputs"};
+    launch_ct_add(a_dev, b_dev, K * 2 * towers, towers, p.logN, ctx->dt.tc, out_dev, (hipStream_t)stream);
   });
 }
 

@@ -110,17 +110,7 @@ __global__ __launch_bounds__(256) void ks_tensor_intt_kernel(const uint64_t* x, 
     lds_put2(sm, p, r2);
   }
   __syncthreads();
-  ntt_inv_block_stages(sm, blkLog, b, logN, itw + (uint64_t)t * N, itwp + (uint64_t)t * N, q);
-  ulonglong2* D = reinterpret_cast<ulonglong2*>(d2c + id);
-  if (sh == 0) {
-    for (uint32_t p = threadIdx.x; p < blk / 2; p += 256) {
-      const ulonglong2 v = lds_get2(sm, p);
-      D[p] = make_ulonglong2(canon4(shoup_lazy(v.x, c.ninv, c.ninv_shoup, q), q),
-                             canon4(shoup_lazy(v.y, c.ninv, c.ninv_shoup, q), q));
-    }
-  } else {  // lazy values in [0, 4q): the columns pass canonicalises
-    for (uint32_t p = threadIdx.x; p < blk / 2; p += 256) D[p] = lds_get2(sm, p);
-  }
+  ks_intt_block_out(sm, blkLog, b, logN, itw + (uint64_t)t * N, itwp + (uint64_t)t * N, c, d2c + id);
 }
 
 // ----------------------------------------------------------------- ModUp ----
@@ -513,32 +503,55 @@ size_t ks_scratch_bytes(uint32_t Ll, uint32_t kP, uint32_t dn, uint32_t alpha, u
   return K * (uint64_t)N * 8 * (2ull * Ll + ext + 2ull * Ll + 2ull * kP + 2ull * Ll) + 64;
 }
 
+KsScratch ks_scratch_layout(const KsArgs& a, uint64_t K, void* scratch) {
+  const uint64_t KN = K << a.logN;
+  KsScratch k;
+  k.d2e = reinterpret_cast<uint64_t*>(scratch);
+  k.d2c = k.d2e + KN * a.Ll;
+  k.ext = k.d2c + KN * a.Ll;
+  uint64_t next = 0;
+  for (uint32_t j = 0; j < a.dn; ++j) next += a.T - std::min(a.alpha, a.Ll - j * a.alpha);
+  k.accQ = k.ext + KN * next;
+  k.accP = k.accQ + KN * 2 * a.Ll;
+  k.z = k.accP + KN * 2 * a.kP;
+  return k;
+}
+
 void launch_eval_mult(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte,
                       const DeviceTables* dtf, const uint64_t* evk, const uint64_t* evk_sh, const uint64_t* x,
                       const uint64_t* y, uint64_t K, uint64_t* out, void* scratch, hipStream_t s) {
+  if (!K) return;
+  const uint32_t blkLog = ntt_block_log(a.logN), sh = a.logN - blkLog;
+  const KsScratch ks = ks_scratch_layout(a, K, scratch);
+  const uint64_t blocks = (K * a.Ll) << sh;
+  if (blocks > 0x7FFFFFFFull) throw Error{SHELFI_ERR_ARG, "EvalMult batch too large"};
+  // tensor -> c0, c1 (out), c2 (EVALUATION) + first INTT pass; the rest is the key switch of c2
+  hipLaunchKernelGGL(ks_tensor_intt_kernel, dim3((uint32_t)blocks), dim3(256), sizeof(uint64_t) << blkLog, s, x, y,
+                     a.Ll, a.logN, blkLog, dtq.ipsi_rev, dtq.ipsi_rev_sh, a.tq, out, ks.d2e, ks.d2c);
+  SHELFI_HIP(hipGetLastError());
+  launch_key_switch(a, dtq, dte, dtf, evk, evk_sh, K, out, scratch, s);
+}
+
+// The HYBRID key switch behind a first pass (the tensor product's, or rotate.hip's automorphism) that
+// left the polynomial to switch in the scratch (d2e: EVALUATION, d2c: after the first INTT pass) and
+// the terms the result is added to in `out`: INTT columns, ModUp, the key inner product, ModDown,
+// out += (u0, u1).
+void launch_key_switch(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,
+                       const uint64_t* evk, const uint64_t* evk_sh, uint64_t K, uint64_t* out, void* scratch,
+                       hipStream_t s) {
   if (!K) return;
   const uint32_t N = 1u << a.logN, bpr = N >> 8;
   const uint32_t blkLog = ntt_block_log(a.logN), sh = a.logN - blkLog;
   const size_t lds = sizeof(uint64_t) << blkLog;
   const uint64_t KN = K * N;
-  uint64_t* d2e = reinterpret_cast<uint64_t*>(scratch);
-  uint64_t* d2c = d2e + KN * a.Ll;
-  uint64_t* ext = d2c + KN * a.Ll;
-  uint64_t next = 0;
-  for (uint32_t j = 0; j < a.dn; ++j) next += a.T - std::min(a.alpha, a.Ll - j * a.alpha);
-  uint64_t* accQ = ext + KN * next;
-  uint64_t* accP = accQ + KN * 2 * a.Ll;
-  uint64_t* z = accP + KN * 2 * a.kP;
+  const KsScratch ks = ks_scratch_layout(a, K, scratch);
+  uint64_t *d2e = ks.d2e, *d2c = ks.d2c, *ext = ks.ext, *accQ = ks.accQ, *accP = ks.accP, *z = ks.z;
   auto grid = [&](uint64_t rows, uint32_t per_row) {
     const uint64_t b = rows * per_row;
-    if (b > 0x7FFFFFFFull) throw Error{SHELFI_ERR_ARG, "EvalMult batch too large"};
+    if (b > 0x7FFFFFFFull) throw Error{SHELFI_ERR_ARG, "key switch batch too large"};
     return dim3((uint32_t)b);
   };
   const uint32_t nb = 1u << sh;
-  // tensor -> c0, c1 (out), c2 (EVALUATION) + first INTT pass; then the INTT columns pass
-  hipLaunchKernelGGL(ks_tensor_intt_kernel, grid(K * a.Ll, nb), dim3(256), lds, s, x, y, a.Ll, a.logN, blkLog,
-                     dtq.ipsi_rev, dtq.ipsi_rev_sh, a.tq, out, d2e, d2c);
-  SHELFI_HIP(hipGetLastError());
   launch_ntt_cols(d2c, K * a.Ll, a.Ll, a.logN, true, dtq, s);
   // ModUp of every digit's foreign towers with their first NTT stages: fused when the ring has
   // a columns pass and digits / special primes have <= 2 towers; else modup_kernel, then a
@@ -713,18 +726,20 @@ void launch_rescale(const DeviceTables& dt, uint32_t Ll, uint32_t logN, const Re
 }
 
 // --------------------------------------------------------- EvalMultKeyGen ----
-// digit j: e_j (nonce (4 << 56) | (j << 16), words [0, N)), a_{j,t} uniform over tower t of
-// Q u P (nonce (4 << 56) | (j << 16) | (1 + t), word pair (2i, 2i+1) -> 128 bits mod q_t)
+// digit j: e_j (nonce base | (j << 16), words [0, N)), a_{j,t} uniform over tower t of
+// Q u P (nonce base | (j << 16) | (1 + t), word pair (2i, 2i+1) -> 128 bits mod q_t); base is
+// the key's domain: 4 << 56 for EvalMult's, (6 << 56) | (g << 24) for the rotation key of g
 __global__ __launch_bounds__(256) void evk_sample_kernel(uint32_t logN, uint32_t T0,
                                                          const TowerConst* __restrict__ te,
                                                          const uint64_t* __restrict__ cdt, int T, Key8 key,
-                                                         uint32_t j, uint64_t* __restrict__ e_out,
+                                                         uint64_t nonce_base, uint32_t j,
+                                                         uint64_t* __restrict__ e_out,
                                                          uint64_t* __restrict__ a_out) {
   const uint32_t N = 1u << logN;
   const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
   if (gid >= (N >> 3)) return;
   const uint32_t j0 = gid * 8;
-  const uint64_t nonce = (4ull << 56) | ((uint64_t)j << 16);
+  const uint64_t nonce = nonce_base | ((uint64_t)j << 16);
   uint64_t re[8];
   chacha20_block(key, j0 >> 3, nonce, re);
   int64_t ev[8];
@@ -761,13 +776,16 @@ __global__ __launch_bounds__(256) void evk_s_ext_kernel(const uint64_t* __restri
   sp[e] = mod_signed_dev(v, c);
 }
 
-// b_j = e_j - a_j s + [t in digit j] (P mod q_t) s^2 (EVALUATION); evk[0][j] = b, evk[1][j] = a
+// b_j = e_j - a_j s + [t in digit j] (P mod q_t) s' (EVALUATION); evk[0][j] = b, evk[1][j] = a.
+// s' is the secret the key switches from: s^2 (galois = 0, EvalMult) or sigma_g(s), s gathered
+// through the automorphism's index map (galois = g, a rotation key)
 __global__ __launch_bounds__(256) void evk_combine_kernel(const uint64_t* __restrict__ e_eval,
                                                           const uint64_t* __restrict__ a_eval,
                                                           const uint64_t* __restrict__ sk,
                                                           const uint64_t* __restrict__ sp,
                                                           const TowerConst* __restrict__ te, EvkGenConst g,
-                                                          uint32_t j, uint64_t* __restrict__ evk) {
+                                                          uint32_t galois, uint32_t j,
+                                                          uint64_t* __restrict__ evk) {
   const uint32_t N = 1u << g.logN, T0 = g.L + g.kP;
   const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= (uint64_t)T0 * N) return;
@@ -776,8 +794,15 @@ __global__ __launch_bounds__(256) void evk_combine_kernel(const uint64_t* __rest
   const uint64_t st = t < g.L ? sk[e] : sp[e - (uint64_t)g.L * N];
   const uint64_t a = a_eval[e];
   uint64_t b = submod(e_eval[e], mulmod_generic(a, st, c), c.q);
-  if (t < g.L && t >= j * g.alpha && t < (j + 1) * g.alpha)
-    b = addmod(b, mulmod_generic(g.pmod[t], mulmod_generic(st, st, c), c), c.q);
+  if (t < g.L && t >= j * g.alpha && t < (j + 1) * g.alpha) {
+    uint64_t sn;
+    if (galois) {  // (only towers of Q carry the P s' term: sp, s over P, needs no gather)
+      sn = sk[((uint64_t)t << g.logN) + galois_src((uint32_t)(e & (N - 1)), galois, g.logN)];
+    } else {
+      sn = mulmod_generic(st, st, c);
+    }
+    b = addmod(b, mulmod_generic(g.pmod[t], sn, c), c.q);
+  }
   const uint64_t TN = (uint64_t)T0 * N;
   evk[(uint64_t)j * TN + e] = b;
   evk[((uint64_t)g.dnum + j) * TN + e] = a;
@@ -789,8 +814,9 @@ size_t evk_scratch_bytes(uint32_t L, uint32_t kP, uint32_t N) {
 
 void launch_evk_keygen(const EvkGenConst& g, const DeviceTables& dtq, const DeviceTables& dte,
                        const uint64_t* cdt, int cdt_len, const uint32_t key[8], const uint64_t* sk,
-                       uint64_t* evk, void* scratch, hipStream_t s) {
+                       uint64_t* evk, void* scratch, hipStream_t s, uint32_t galois) {
   const uint32_t N = 1u << g.logN, T0 = g.L + g.kP;
+  const uint64_t nonce_base = galois ? (6ull << 56) | ((uint64_t)galois << 24) : (4ull << 56);
   uint64_t* eb = reinterpret_cast<uint64_t*>(scratch);
   uint64_t* ab = eb + (uint64_t)T0 * N;
   uint64_t* sp = ab + (uint64_t)T0 * N;
@@ -807,11 +833,11 @@ void launch_evk_keygen(const EvkGenConst& g, const DeviceTables& dtq, const Devi
   const uint64_t tn = (uint64_t)T0 * N;
   for (uint32_t j = 0; j < g.dnum; ++j) {
     hipLaunchKernelGGL(evk_sample_kernel, dim3((N / 8 + 255) / 256), dim3(256), 0, s, g.logN, T0, dte.tc, cdt,
-                       cdt_len, k8, j, eb, ab);
+                       cdt_len, k8, nonce_base, j, eb, ab);
     SHELFI_HIP(hipGetLastError());
     launch_ntt(eb, T0, T0, g.logN, false, dte, s);
     hipLaunchKernelGGL(evk_combine_kernel, dim3((uint32_t)((tn + 255) / 256)), dim3(256), 0, s, eb, ab, sk, sp,
-                       dte.tc, g, j, evk);
+                       dte.tc, g, galois, j, evk);
     SHELFI_HIP(hipGetLastError());
   }
 }

@@ -467,6 +467,26 @@ size_t ks_scratch_bytes(uint32_t Ll, uint32_t kP, uint32_t dn, uint32_t alpha, u
 void launch_eval_mult(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte,
                       const DeviceTables* dtf, const uint64_t* evk, const uint64_t* evk_sh, const uint64_t* x,
                       const uint64_t* y, uint64_t K, uint64_t* out, void* scratch, hipStream_t s);
+// The key switch alone (launch_eval_mult's chain behind its tensor pass): a first pass has left the
+// polynomial to switch, [K][Ll][N], in the scratch -- d2e in EVALUATION, d2c after the first INTT
+// pass (ks_intt_block_out) -- and the terms the result is added to in out [K][2][Ll][N];
+// out += KeySwitch(d2) under the key (evk, evk_sh) of the evaluation key's layout.
+struct KsScratch {
+  uint64_t *d2e, *d2c, *ext, *accQ, *accP, *z;
+};
+KsScratch ks_scratch_layout(const KsArgs& a, uint64_t K, void* scratch);
+void launch_key_switch(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,
+                       const uint64_t* evk, const uint64_t* evk_sh, uint64_t K, uint64_t* out, void* scratch,
+                       hipStream_t s);
+// Rotation (rotate.hip): out = (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)) under the rotation key of
+// the Galois element g; ct, out [K][2][Ll][N], not overlapping; scratch = ks_scratch_bytes(.., K).
+void launch_rotate(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,
+                   const uint64_t* rk, const uint64_t* rk_sh, uint32_t g, const uint64_t* ct, uint64_t K,
+                   uint64_t* out, void* scratch, hipStream_t s);
+// EvalAdd of two ciphertext batches: out = a + b mod q_t over rows = K * 2 * Ll polynomials (out may
+// be a or b)
+void launch_ct_add(const uint64_t* a, const uint64_t* b, uint64_t rows, uint32_t Ll, uint32_t logN,
+                   const TowerConst* tq, uint64_t* out, hipStream_t s);
 // ModReduce: in [K][2][Ll][N] -> out [K][2][Ll-1][N] (EVAL); qlinv[t] = q_{Ll-1}^-1 mod q_t
 struct RescaleConst {
   uint64_t ql;  // the dropped modulus q_{Ll-1}
@@ -482,8 +502,10 @@ struct EvkGenConst {
   uint32_t L, kP, dnum, alpha, logN;
 };
 size_t evk_scratch_bytes(uint32_t L, uint32_t kP, uint32_t N);
+// galois = 0: the EvalMult key (s^2 -> s, nonce domain 4); galois = g: the rotation key of the
+// Galois element g (sigma_g(s) -> s, nonce domain (6 << 56) | (g << 24))
 void launch_evk_keygen(const EvkGenConst& g, const DeviceTables& dtq, const DeviceTables& dte,
                        const uint64_t* cdt, int cdt_len, const uint32_t key[8], const uint64_t* sk,
-                       uint64_t* evk, void* scratch, hipStream_t s);
+                       uint64_t* evk, void* scratch, hipStream_t s, uint32_t galois = 0);
 
 }  // namespace shelfi

@@ -404,6 +404,49 @@ int shelfi_dev_decrypt_level(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, 
 int shelfi_dev_decrypt_sum(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t terms, double scale,
                            size_t n, double* out_dev, void* stream);
 
+/* ---- slot rotations and EvalSum (the reference's code/mkhe/mkhe.cpp) -------------- *
+ * A rotation by index r is the automorphism X -> X^g, g = 5^r mod 2N (r < 0: the inverse),
+ * followed by the HYBRID key switch of EvalMult under a rotation key sigma_g(s) -> s of the
+ * evaluation key's layout (shelfi_eval_key_words words).  With this library's encoding it sends
+ * slot vector x to out[i] = x[(i + r) mod batch] (r > 0 rotates left), for sparse packing too.
+ * A context holds up to 64 rotation keys, keyed by g; a key reload or regeneration
+ * (shelfi_keygen, shelfi_load, shelfi_set_keys, shelfi_multiparty_keygen) drops them.  A missing
+ * key is SHELFI_ERR_STATE.  Whether PALISADE permutes before or after switching, and its own
+ * EvalSumKeyGen index list, are not pinned. */
+/* Host-only: PALISADE's FindAutomorphismIndex2nComplex: g = 5^index mod 2N, or its inverse for a
+ * negative index; index 0 gives 1.  ring_dim a power of two in 2^2..2^17, |index| < ring_dim / 2. */
+int shelfi_galois_element(uint32_t ring_dim, int32_t index, uint32_t* g);
+/* cc->EvalAtIndexKeyGen(sk, indices) (mkhe.cpp:124) on the device: adds the rotation keys of n
+ * indices (|index| < batch) to those held.  Index 0 is skipped; an index whose key is held is
+ * generated again (identically under a seed: the stream is the context's seeded ChaCha20 in a
+ * domain of its own, nonce (6 << 56) | (g << 24) | (digit << 16) | (1 + tower), tower field 0
+ * for the error).  A 65th key: SHELFI_ERR_ARG. */
+int shelfi_rotation_keygen(shelfi_ctx* ctx, const int32_t* indices, size_t n);
+/* cc->EvalSumKeyGen(sk) (mkhe.cpp:274): the keys shelfi_dev_eval_sum needs up to n = batch,
+ * indices 1, 2, 4, ..., batch / 2. */
+int shelfi_eval_sum_keygen(shelfi_ctx* ctx);
+/* The indices held (as first given for each g): *n = their count, the first min(cap, *n) in out
+ * (out may be NULL when cap is 0). */
+int shelfi_rotation_key_indices(const shelfi_ctx* ctx, int32_t* out, size_t cap, size_t* n);
+/* Export / import of one rotation key, [2][dnum][L + num_special][N] like the evaluation key (a
+ * party of mkhe.cpp:284-317's protocols imports the joint key this way).  A residue >= its
+ * modulus: SHELFI_ERR_FORMAT. */
+int shelfi_get_rotation_key(const shelfi_ctx* ctx, int32_t index, uint64_t* key);
+int shelfi_set_rotation_key(shelfi_ctx* ctx, int32_t index, const uint64_t* key);
+/* cc->EvalAtIndex(ct, index): ct_dev, out_dev [K][2][towers][N] in HBM, not overlapping (index 0
+ * is a copy; out may then be ct).  Scale and depth are the input's. */
+int shelfi_dev_rotate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, int32_t index,
+                      uint64_t* out_dev, void* stream);
+/* cc->EvalSum(ct, n) (mkhe.cpp:372), n a power of two in 1..batch: log2(n) steps
+ * acc <- acc + Rotate(acc, 2^i), i = 0 .. log2(n) - 1; slot i then holds
+ * sum_{j < n} x[(i + j) mod batch].  n = 1 is a copy.  ct_dev and out_dev must not overlap. */
+int shelfi_dev_eval_sum(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, uint32_t n,
+                        uint64_t* out_dev, void* stream);
+/* cc->EvalAdd(ct_a, ct_b) (mkhe.cpp:168, :368): out = a + b mod q_t over [K][2][towers][N]; out may be a
+ * or b.  Needs no keys and no scratch: it returns with the work enqueued on `stream`. */
+int shelfi_dev_add(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev, size_t K, uint32_t towers,
+                   uint64_t* out_dev, void* stream);
+
 /* ---- threshold CKKS (the reference's code/mkhe/mkhe.cpp RunCKKS, lines 188-465) ---- *
  * P parties hold additive shares s_i of one secret key; a ciphertext under the joint public key
  * decrypts only when every party contributes a partial decryption.  Encrypt and
