@@ -390,6 +390,12 @@ class CKKS(Scheme):
         check(self._lib.shelfi_set_rotation_key(self._ctx, int(r), key.ctypes.data_as(_lib.u64p)),
               "set_rotation_key")
 
+    def eval_chunk_count(self) -> int:
+        """Launch chains the last successful device.mult / rescale / rotate / eval_sum of this context
+        took (shelfi_eval_chunk_count): 1 unless the batch's scratch exceeds SHELFI_EVAL_CHUNK_MIB
+        (2048 by default); 0 after a call that enqueued none (K = 0, rotate by 0, eval_sum with n = 1)."""
+        return int(self._lib.shelfi_eval_chunk_count(self._ctx))
+
     # ------------------------------------------------------------ hot path --
     def _take(self, ptr: "_lib.u8p", n: int) -> bytes:
         try:

@@ -192,6 +192,7 @@ SIGNATURES = {
                                     C.c_void_p]),
     "shelfi_dev_eval_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
                                       C.c_void_p]),
+    "shelfi_eval_chunk_count": (C.c_uint64, [C.c_void_p]),
     "shelfi_dev_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                  C.c_void_p]),
     # threshold CKKS (mkhe.cpp RunCKKS): key chain, partial decryption, fusion (threshold.hip)

@@ -405,8 +405,10 @@ void load_evalkey_if_present(shelfi_ctx* ctx, const std::string& dir) {
   }
 }
 
+// Ciphertexts per launch chain: K split evenly over the fewest chains whose scratch fits the budget
+// (SHELFI_EVAL_CHUNK_MIB, 2048 by default; read from the switches' snapshot, never the environment).
 static uint64_t chunk_of(uint64_t K, size_t per_ct) {
-  const uint64_t cap = std::max<uint64_t>(1, (2048ull << 20) / std::max<size_t>(per_ct, 1));
+  const uint64_t cap = std::max<uint64_t>(1, (switches().eval_chunk_mib << 20) / std::max<size_t>(per_ct, 1));
   const uint64_t n = (K + cap - 1) / cap;
   return n ? (K + n - 1) / n : 1;
 }
@@ -667,7 +669,10 @@ int shelfi_dev_mult(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_de
     if (!ctx->ev || !ctx->ev->evk)
       throw Error{SHELFI_ERR_STATE, "no evaluation key: call evalMultKeyGen() first"};
     LevelState& l = level(ctx, towers);
-    if (!K) return;
+    if (!K) {
+      ctx->eval_chunk_count = 0;
+      return;
+    }
     // out may alias a or b exactly (each workgroup reads its inputs before writing that
     // ciphertext's output); a shifted overlap would let one chunk's writes corrupt inputs
     // another has not read yet
@@ -682,12 +687,15 @@ int shelfi_dev_mult(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_de
     void* scratch =
         ensure(ctx->scratch, ctx->scratch_bytes, ks_scratch_bytes(a.Ll, a.kP, a.dn, a.alpha, N, kc_max));
     const uint64_t ctw = 2ull * towers * N;
+    uint64_t chains = 0;
     for (uint64_t k0 = 0; k0 < K; k0 += kc_max) {
       const uint64_t kc = std::min<uint64_t>(kc_max, K - k0);
       launch_eval_mult(a, ctx->dt, l.ext, l.dtf, ctx->ev->evk, ctx->ev->evk_sh, a_dev + k0 * ctw,
                        b_dev + k0 * ctw, kc, out_dev + k0 * ctw, scratch, s);
+      ++chains;
     }
     SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
+    ctx->eval_chunk_count = chains;
   });
 }
 
@@ -699,7 +707,10 @@ int shelfi_dev_rescale(shelfi_ctx* ctx, const uint64_t* in_dev, size_t K, uint32
     DeviceGuard g(ctx->device);
     const Params& p = ctx->p;
     if (towers < 2 || towers > p.L) throw Error{SHELFI_ERR_ARG, "ModReduce needs 2..L towers"};
-    if (!K) return;
+    if (!K) {
+      ctx->eval_chunk_count = 0;
+      return;
+    }
     const uint64_t in_words = 2ull * towers * p.N * K, out_words = 2ull * (towers - 1) * p.N * K;
     if (out_dev < in_dev + in_words && in_dev < out_dev + out_words)
       throw Error{SHELFI_ERR_ARG, "ModReduce input and output must not overlap"};
@@ -712,12 +723,15 @@ int shelfi_dev_rescale(shelfi_ctx* ctx, const uint64_t* in_dev, size_t K, uint32
     hipStream_t s = (hipStream_t)stream;
     const uint64_t kc_max = chunk_of(K, rescale_scratch_bytes(towers, p.N, 1));
     void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, rescale_scratch_bytes(towers, p.N, kc_max));
+    uint64_t chains = 0;
     for (uint64_t k0 = 0; k0 < K; k0 += kc_max) {
       const uint64_t kc = std::min<uint64_t>(kc_max, K - k0);
       launch_rescale(ctx->dt, towers, p.logN, rc, in_dev + k0 * 2ull * towers * p.N, kc,
                      out_dev + k0 * 2ull * (towers - 1) * p.N, scratch, s);
+      ++chains;
     }
     SHELFI_HIP(hipStreamSynchronize(s));
+    ctx->eval_chunk_count = chains;
   });
 }
 
@@ -737,28 +751,36 @@ int shelfi_dev_rotate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_
     const uint64_t ctw = 2ull * towers * N;
     if (!index) {  // the identity: a copy (out may be the input itself)
       level_q(ctx, towers);
-      if (!K || out_dev == ct_dev) return;
-      if (overlaps(ct_dev, out_dev, ctw * K))
-        throw Error{SHELFI_ERR_ARG, "rotation input and output must not overlap"};
-      SHELFI_HIP(hipMemcpyAsync(out_dev, ct_dev, ctw * K * 8, hipMemcpyDeviceToDevice, s));
-      SHELFI_HIP(hipStreamSynchronize(s));
+      if (K && out_dev != ct_dev) {
+        if (overlaps(ct_dev, out_dev, ctw * K))
+          throw Error{SHELFI_ERR_ARG, "rotation input and output must not overlap"};
+        SHELFI_HIP(hipMemcpyAsync(out_dev, ct_dev, ctw * K * 8, hipMemcpyDeviceToDevice, s));
+        SHELFI_HIP(hipStreamSynchronize(s));
+      }
+      ctx->eval_chunk_count = 0;  // a copy: no launch chain
       return;
     }
     LevelState& l = level(ctx, towers);
     const EvalState::RotKey& rk = require_rot(ctx, index, g);
-    if (!K) return;
+    if (!K) {
+      ctx->eval_chunk_count = 0;
+      return;
+    }
     // the gather reads whole rows of the input while other workgroups write the output
     if (overlaps(ct_dev, out_dev, ctw * K)) throw Error{SHELFI_ERR_ARG, "rotation input and output must not overlap"};
     const KsArgs& a = l.args;
     const uint64_t kc_max = chunk_of(K, ks_scratch_bytes(a.Ll, a.kP, a.dn, a.alpha, N, 1));
     void* scratch =
         ensure(ctx->scratch, ctx->scratch_bytes, ks_scratch_bytes(a.Ll, a.kP, a.dn, a.alpha, N, kc_max));
+    uint64_t chains = 0;
     for (uint64_t k0 = 0; k0 < K; k0 += kc_max) {
       const uint64_t kc = std::min<uint64_t>(kc_max, K - k0);
       launch_rotate(a, ctx->dt, l.ext, l.dtf, rk.key, rk.key_sh, g, ct_dev + k0 * ctw, kc, out_dev + k0 * ctw,
                     scratch, s);
+      ++chains;
     }
     SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
+    ctx->eval_chunk_count = chains;
   });
 }
 
@@ -779,13 +801,19 @@ int shelfi_dev_eval_sum(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint3
     };
     std::vector<Step> steps;  // every key is looked up before anything is enqueued
     level_q(ctx, towers);
+    // a chain that cannot key-switch says so, before the keys it can never hold are missed
+    if (n > 1 && !eval_state(ctx).ks_error.empty()) throw Error{SHELFI_ERR_ARG, eval_state(ctx).ks_error};
     for (uint32_t r = 1; r < n; r <<= 1) {
       const uint32_t g = rotation_galois(ctx, (int32_t)r);
       steps.push_back(Step{g, &require_rot(ctx, (int32_t)r, g)});
     }
-    if (!K) return;
+    if (!K) {
+      ctx->eval_chunk_count = 0;
+      return;
+    }
     if (overlaps(ct_dev, out_dev, ctw * K)) throw Error{SHELFI_ERR_ARG, "EvalSum input and output must not overlap"};
     SHELFI_HIP(hipMemcpyAsync(out_dev, ct_dev, ctw * K * 8, hipMemcpyDeviceToDevice, s));
+    uint64_t chains = 0;  // n = 1 is the copy alone
     if (!steps.empty()) {
       LevelState& l = level(ctx, towers);
       const KsArgs& a = l.args;
@@ -802,10 +830,18 @@ int shelfi_dev_eval_sum(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint3
           launch_rotate(a, ctx->dt, l.ext, l.dtf, st.rk->key, st.rk->key_sh, st.g, acc, kc, rot, scratch, s);
           launch_ct_add(acc, rot, kc * 2 * towers, towers, ctx->p.logN, a.tq, acc, s);
         }
+        ++chains;
       }
     }
     SHELFI_HIP(hipStreamSynchronize(s));
+    ctx->eval_chunk_count = chains;
   });
+}
+
+uint64_t shelfi_eval_chunk_count(const shelfi_ctx* ctx) {
+  if (!ctx) return 0;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return ctx->eval_chunk_count;
 }
 
 int shelfi_dev_add(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev, size_t K, uint32_t towers,

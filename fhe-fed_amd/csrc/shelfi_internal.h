@@ -80,6 +80,7 @@ struct Switches {
   uint32_t wavg_strands = 0;   // SHELFI_WAVG_STRANDS=n: wavg_packed's blocks in n interleaved strands (0: in order)
   int arena_stager = -1;       // SHELFI_ARENA_STAGER=0|1 (-1: by upload shape)
   uint64_t dev_chunk_mib = 4096;  // SHELFI_DEV_CHUNK_MIB: device encrypt / decrypt scratch per chain
+  uint64_t eval_chunk_mib = 2048;  // SHELFI_EVAL_CHUNK_MIB: EvalMult / ModReduce / Rotate / EvalSum scratch per chain
   uint64_t wavg_chunk_mib = 0;    // SHELFI_WAVG_CHUNK_MIB: bytes-API aggregation chunk per learner group
                                   // (0: 32 MiB per learner with direct uploads, 128 per group through the ring)
   uint64_t stage_slot_mib = 16;   // SHELFI_STAGE_SLOT_MIB: pinned staging-ring slot (DMA granule)
@@ -269,6 +270,7 @@ struct shelfi_ctx {
   int decode_exact = 0;          // shelfi_set_decode_exact: every decrypt over every tower, exact CRT
   uint64_t decode_redo_count = 0;  // decrypt calls whose fast pass was redone exactly (shelfi_decode_redo_count)
   uint64_t encode_redo_count = 0;  // encrypt calls redone on the large-value path (shelfi_encode_redo_count)
+  uint64_t eval_chunk_count = 0;   // launch chains of the last mult / rescale / rotate / eval_sum (shelfi_eval_chunk_count)
   int last_log_error = -1;       // of the last flooded decrypt, -1 if none
   bool log_error_pending = false;  // dev_flag[2] holds a newer one, read on demand (shelfi_decode_log_error)
   std::string pal_ctx_obj;       // PALISADE keys: embedded context object (§8 f1)

@@ -52,6 +52,8 @@ void reload_switches() {
   s.arena_stager = env_choice("SHELFI_ARENA_STAGER", {0, 1}, -1);
   if (const char* e = getenv("SHELFI_DEV_CHUNK_MIB"))
     if (atoll(e) > 0) s.dev_chunk_mib = (uint64_t)atoll(e);
+  if (const char* e = getenv("SHELFI_EVAL_CHUNK_MIB"))
+    if (atoll(e) > 0) s.eval_chunk_mib = (uint64_t)atoll(e);
   if (const char* e = getenv("SHELFI_WAVG_CHUNK_MIB"))
     if (atoll(e) > 0) s.wavg_chunk_mib = (uint64_t)atoll(e);
   if (const char* e = getenv("SHELFI_STAGE_SLOT_MIB"))

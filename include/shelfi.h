@@ -442,6 +442,11 @@ int shelfi_dev_rotate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_
  * sum_{j < n} x[(i + j) mod batch].  n = 1 is a copy.  ct_dev and out_dev must not overlap. */
 int shelfi_dev_eval_sum(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, uint32_t n,
                         uint64_t* out_dev, void* stream);
+/* The number of launch chains (chunks of the batch, each within the SHELFI_EVAL_CHUNK_MIB scratch budget,
+ * 2048 by default) the last successful shelfi_dev_mult, shelfi_dev_rescale, shelfi_dev_rotate or
+ * shelfi_dev_eval_sum on this context took.  0 after a call that enqueued no chain (K = 0, index 0,
+ * n = 1); a refused call leaves it unchanged.  For tests of the chunking. */
+uint64_t shelfi_eval_chunk_count(const shelfi_ctx* ctx);
 /* cc->EvalAdd(ct_a, ct_b) (mkhe.cpp:168, :368): out = a + b mod q_t over [K][2][towers][N]; out may be a
  * or b.  Needs no keys and no scratch: it returns with the work enqueued on `stream`. */
 int shelfi_dev_add(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev, size_t K, uint32_t towers,

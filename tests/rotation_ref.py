@@ -64,6 +64,21 @@ def gather_index(N, g):
     return brev(((int(g) * (2 * brev(j) + 1)) % (2 * N)) >> 1)
 
 
+def sweep_indices(batch):
+    """The rotation indices the permutation sweeps run at a batch size (tests/test_gpu_rotate_gather.py,
+    tests/test_rotation_ref.py): the small ones of both signs, those around batch / 2 and batch / 4,
+    the largest, and sixteen more drawn from a seeded generator over (-batch, batch), none 0 or repeated."""
+    fixed = [1, -1, 2, -2, 3, -3, 7, -7, batch // 2, batch // 2 + 1, batch // 2 - 1, batch // 4 + 1,
+             batch - 1, -(batch - 1), batch - 2]
+    rng = np.random.default_rng([20, batch])
+    more = []
+    while len(more) < 16:
+        r = int(rng.integers(1 - batch, batch))
+        if r and r not in fixed and r not in more:
+            more.append(r)
+    return fixed + more
+
+
 def rotate_ref(ct, r, key, q, psi):
     """Rotate(ct, r) at ct's level: (sigma(c0) + u0, u1), (u0, u1) = KeySwitch(sigma(c1)) under `key`
     ([2][dnum][L + kP][N]); ct [K][2][l][N], q / psi the whole chain."""

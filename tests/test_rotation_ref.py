@@ -1,7 +1,11 @@
 """Slot rotations and EvalSum without a device: the library's Galois elements, and
 the yardstick tests/test_gpu_rotate.py measures the kernels with (tests/rotation_ref.py) checked for
 what it must mean -- a reference rotation decrypts to the rolled slots and a reference EvalSum to the
-sliding sums, at full and at sparse packing."""
+sliding sums, at full and at sparse packing.
+
+Also the two yardsticks of tests/test_gpu_rotate_gather.py: with c1 = 0 a reference rotation is the pure
+gather of c0 beside a zero component under any key, and the device's 32-bit form of the gather index
+(dev_common.h galois_src, restated here in numpy) is R.gather_index on every ring for the swept indices."""
 import functools
 
 import numpy as np
@@ -76,3 +80,54 @@ def test_reference_rotation_and_eval_sum_decrypt_to_rolled_slots(slots):
         dec = O.decrypt_vector(tot, sk, q, psi, slots, delta, 2 * slots).reshape(2, slots)
         exp = sum(np.roll(xs, -j, axis=1) for j in range(n))
         assert np.abs(dec - exp).max() < 1e-7 * n
+
+
+def test_rotation_of_a_zero_second_component_is_the_gather_under_any_key():
+    """KeySwitch(sigma_g(0)) = 0 whatever the key holds: Rotate((c0, 0), r) = (c0[..., src_g], 0), under the
+    oracle's evaluation key (not a rotation key at all) and under a key made for r."""
+    n, towers = 1 << 11, 3
+    q, psi = O.params_generate(n, towers, 52, 60)
+    s, e, a = O.sample_keygen(SEED, n, q)
+    sk, _ = O.keygen(s, e, a, q, psi)
+    evk = O.evk_keygen(SEED, sk, q, psi)
+    rng = np.random.default_rng(3)
+    ct = np.zeros((2, 2, towers, n), np.uint64)
+    for t in range(towers):
+        ct[:, 0, t] = rng.integers(0, int(q[t]), (2, n), dtype=np.uint64)
+    batch = n // 2
+    for r in (1, -3, batch // 2 + 1, batch - 1):
+        src = R.gather_index(n, R.galois(n, r))
+        for key in (evk, R.rot_key_from_evk(evk, r, sk, q, psi)):
+            out = R.rotate_ref(ct, r, key, q, psi)
+            assert not out[:, 1].any(), r
+            assert np.array_equal(out[:, 0], ct[:, 0][..., src]), r
+
+
+def _brev32(v):
+    v = np.asarray(v, np.uint64)
+    r = np.zeros_like(v)
+    for i in range(32):
+        r |= ((v >> np.uint64(i)) & np.uint64(1)) << np.uint64(31 - i)
+    return r
+
+
+def device_galois_src(n, g):
+    """dev_common.h galois_src for every j < n, step for step: a 32-bit bit reversal shifted right by
+    32 - logN, the product g e kept to its low 32 bits and then masked with 2N - 1, and the reversal again."""
+    logn = n.bit_length() - 1
+    m32 = np.uint64(0xFFFFFFFF)
+    j = np.arange(n, dtype=np.uint64)
+    e = (np.uint64(2) * (_brev32(j) >> np.uint64(32 - logn)) + np.uint64(1)) & m32
+    ge = ((np.uint64(g) * e) & m32) & np.uint64(2 * n - 1)  # g, e < 2^18: the uint64 product is exact
+    return (_brev32(ge >> np.uint64(1)) >> np.uint64(32 - logn)).astype(np.int64)
+
+
+@pytest.mark.parametrize("logn", range(11, 18))
+def test_device_form_of_the_gather_index(logn):
+    n = 1 << logn
+    gs = [R.galois(n, r) for r in R.sweep_indices(n // 2)]
+    if logn == 15:
+        gs += [R.galois(n, r) for r in R.sweep_indices(4096)]  # the sparse context's list
+    assert any(g > n for g in gs) and (logn < 16 or any(g >= 1 << 16 for g in gs))
+    for g in gs:
+        assert np.array_equal(device_galois_src(n, g), R.gather_index(n, g)), (n, g)
