@@ -2,7 +2,13 @@
 FFT's output in its last pass; decode_flood_kernel for batches below 2^6 slots) against the
 oracle's restatement with the same seeded noise stream.  Tolerance 1e-14 absolute:
 the noise (~1e-13) is generated with GPU vs glibc log/sincos (ulp-level differences)
-and sigma is a tree vs sequential sum; everything else is the exact decode."""
+and sigma is a tree vs sequential sum; everything else is the exact decode.
+
+These are four shapes of real ciphertexts at m_factor = 1, where the noise is about the size of the
+tolerance.  tests/test_gpu_decode_flood.py holds the same kernels to the oracle where the noise dominates
+(m_factor = 2^40 - 1, bound 2^-10 of the noise), on every dispatch branch (1 to 2^16 slots, the whole-vector
+path, SHELFI_FFT_CT=0), with planted statistics (tests/flood_cases.py: mean, self-paired slots, pairing,
+floor, the p - 5 threshold, sqrt(M + 1)), at 30-bit scale, and across the device and bytes chunk seams."""
 import os
 
 import numpy as np
