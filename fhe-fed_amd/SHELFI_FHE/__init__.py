@@ -390,6 +390,77 @@ class CKKS(Scheme):
         check(self._lib.shelfi_set_rotation_key(self._ctx, int(r), key.ctypes.data_as(_lib.u64p)),
               "set_rotation_key")
 
+    # ------------- multiparty evaluation keys for threshold CKKS (mkhe.cpp:271-317) --
+    def _mk_key(self, key, what: str) -> np.ndarray:
+        """A key argument of the multiparty calls: uint64 [2][dnum][L + kP][N], nothing converted."""
+        k = np.asarray(key)
+        if k.dtype != np.uint64:
+            raise ValueError("%s must be uint64, not %s" % (what, k.dtype))
+        shape = self._rotation_key_shape()
+        if k.shape != shape:
+            raise ValueError("%s must be [2][dnum][L + kP][N] = %s, not %s" % (what, shape, k.shape))
+        return np.ascontiguousarray(k)
+
+    def multiKeySwitchGen(self, prev=None, index: int = 0) -> np.ndarray:
+        """This party's round-1 share of a joint key: cc->KeySwitchGen(sk, sk) for the lead party
+        (prev=None, mkhe.cpp:271), cc->MultiKeySwitchGen(sk, sk, prev) for the others (mkhe.cpp:296).
+        index 0 is the EvalMult share; index r != 0 the share of rotation r's key.  A follower
+        copies prev's a-vector.  Installs nothing."""
+        out = np.zeros(self._rotation_key_shape(), np.uint64)
+        pp = None if prev is None else self._mk_key(prev, "the previous key")
+        check(self._lib.shelfi_multi_key_switch_gen(self._ctx, int(index),
+                                                    None if pp is None else pp.ctypes.data_as(_lib.u64p),
+                                                    out.ctypes.data_as(_lib.u64p)), "multiKeySwitchGen")
+        return out
+
+    def multiEvalSumKeyGen(self, prev=None) -> dict:
+        """cc->MultiEvalSumKeyGen(sk, prev) (mkhe.cpp:284; cc->EvalSumKeyGen, :274, for the lead party,
+        prev=None): this party's shares of the rotation keys EvalSum needs, {index: key} for
+        1, 2, 4, ..., batch / 2."""
+        batch = self.info()["batch"]
+        idx = [1 << i for i in range(batch.bit_length()) if (1 << i) < batch]  # evalSumKeyGen's list
+        if prev is not None and sorted(prev) != idx:
+            raise ValueError("the previous EvalSum key map must hold the indices 1, 2, 4, ..., batch / 2")
+        return {r: self.multiKeySwitchGen(None if prev is None else prev[r], r) for r in idx}
+
+    def _mk_add(self, keys, sum_a: bool, what: str) -> np.ndarray:
+        ks = [self._mk_key(k, "every key") for k in keys]
+        if not 1 <= len(ks) <= 16:
+            raise ValueError("%s takes 1..16 keys, not %d" % (what, len(ks)))
+        arr = (_lib.u64p * len(ks))(*[k.ctypes.data_as(_lib.u64p) for k in ks])
+        out = np.zeros(self._rotation_key_shape(), np.uint64)
+        check(self._lib.shelfi_multi_add_eval_keys(self._ctx, arr, len(ks), 1 if sum_a else 0,
+                                                   out.ctypes.data_as(_lib.u64p)), what)
+        return out
+
+    def multiAddEvalKeys(self, keys) -> np.ndarray:
+        """cc->MultiAddEvalKeys (mkhe.cpp:298) over 1..16 round-1 shares: b-vectors summed, the
+        a-vectors must be identical (ValueError otherwise).  For a rotation index the sum over all
+        parties is the joint rotation key; for index 0 it is round 2's input."""
+        return self._mk_add(keys, False, "multiAddEvalKeys")
+
+    def multiAddEvalSumKeys(self, maps) -> dict:
+        """cc->MultiAddEvalSumKeys (mkhe.cpp:288): multiAddEvalKeys per index over 1..16 parties'
+        multiEvalSumKeyGen maps -> the joint {index: key} for set_rotation_key."""
+        maps = list(maps)
+        if not maps or any(sorted(m) != sorted(maps[0]) for m in maps):
+            raise ValueError("multiAddEvalSumKeys needs 1..16 key maps over the same indices")
+        return {r: self._mk_add([m[r] for m in maps], False, "multiAddEvalSumKeys") for r in sorted(maps[0])}
+
+    def multiMultEvalKey(self, joint) -> np.ndarray:
+        """cc->MultiMultEvalKey(joint, sk) (mkhe.cpp:307, :311): round 2 of the EvalMult key, this
+        party's (b s_i + e2, a s_i + e1) of the summed round-1 shares."""
+        jj = self._mk_key(joint, "the joint key")
+        out = np.zeros(self._rotation_key_shape(), np.uint64)
+        check(self._lib.shelfi_multi_mult_eval_key(self._ctx, jj.ctypes.data_as(_lib.u64p),
+                                                   out.ctypes.data_as(_lib.u64p)), "multiMultEvalKey")
+        return out
+
+    def multiAddEvalMultKeys(self, keys) -> np.ndarray:
+        """cc->MultiAddEvalMultKeys (mkhe.cpp:314) over every party's multiMultEvalKey answer: both
+        vectors summed -> the EvalMult key of the joint secret, for set_eval_key."""
+        return self._mk_add(keys, True, "multiAddEvalMultKeys")
+
     def eval_chunk_count(self) -> int:
         """Launch chains the last successful device.mult / rescale / rotate / eval_sum of this context
         took (shelfi_eval_chunk_count): 1 unless the batch's scratch exceeds SHELFI_EVAL_CHUNK_MIB

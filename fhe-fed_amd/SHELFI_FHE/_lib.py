@@ -211,6 +211,10 @@ SIGNATURES = {
     "shelfi_partial_blob_pack": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_double,
                                            C.c_uint64, C.c_uint64, C.c_int, u64p, C.POINTER(u8p),
                                            C.POINTER(C.c_size_t)]),
+    # multiparty evaluation keys (mkhe.cpp:271-317; eval.cpp, multikey.hip)
+    "shelfi_multi_key_switch_gen": (C.c_int, [C.c_void_p, C.c_int32, u64p, u64p]),
+    "shelfi_multi_add_eval_keys": (C.c_int, [C.c_void_p, C.POINTER(u64p), C.c_size_t, C.c_int, u64p]),
+    "shelfi_multi_mult_eval_key": (C.c_int, [C.c_void_p, u64p, u64p]),
     "shelfi_fft_twiddles": (C.c_int, [C.c_uint32, f64p, f64p, f64p, f64p]),
     "shelfi_gauss_cdt": (C.c_int, [C.c_double, u64p, C.c_int]),
 }

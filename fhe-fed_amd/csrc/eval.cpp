@@ -1,7 +1,8 @@
 // eval.cpp — C ABI of SURVEY §8 f4: EvalMultKeyGen, EvalMult (ct x ct) with HYBRID
 // relinearization, ModReduce, and the per-level tables they (and decrypt at a level) use; and of
 // the slot rotations built on the same key switch (mkhe.cpp:124, :274, :372):
-// rotation keys, Rotate, EvalSum and the plain EvalAdd (rotate.hip).
+// rotation keys, Rotate, EvalSum and the plain EvalAdd (rotate.hip); and of the multiparty
+// evaluation-key protocols of threshold CKKS (mkhe.cpp:271-317; multikey.hip).
 //
 // None of this is on the reference's aggregation path (ckks.cpp:26 fixes multDepth = 1 and
 // computeWeightedAverage only multiplies by constants); it is the general-circuit part of
@@ -460,11 +461,7 @@ size_t shelfi_eval_key_words(const shelfi_ctx* ctx) {
 namespace shelfi {
 // A key-switching key s' -> s on the device, read back: galois = 0: s' = s^2 (EvalMultKeyGen);
 // galois = g: s' = sigma_g(s) (a rotation key).  ctx lock held, device set.
-static std::vector<uint64_t> switch_keygen(shelfi_ctx* ctx, uint32_t galois) {
-  require_keys(ctx);
-  const Params& p = ctx->p;
-  EvalState& ev = eval_state(ctx);
-  LevelState& l = level(ctx, p.L);
+static EvkGenConst evk_gen_const(const Params& p, const EvalState& ev) {
   EvkGenConst gc{};
   gc.q0 = p.q[0];
   for (uint32_t t = 0; t < p.L; ++t) {
@@ -476,11 +473,25 @@ static std::vector<uint64_t> switch_keygen(shelfi_ctx* ctx, uint32_t galois) {
   gc.dnum = ev.dnum;
   gc.alpha = ev.alpha;
   gc.logN = p.logN;
-  uint32_t key[8];
+  return gc;
+}
+
+// the ChaCha20 key of a key-generating call: the context's seed, or OS entropy per call
+static void stream_key(const shelfi_ctx* ctx, uint32_t key[8]) {
   if (ctx->seed)
     seed_to_key(ctx->seed, key);
   else
     os_random(key, 32);
+}
+
+static std::vector<uint64_t> switch_keygen(shelfi_ctx* ctx, uint32_t galois) {
+  require_keys(ctx);
+  const Params& p = ctx->p;
+  EvalState& ev = eval_state(ctx);
+  LevelState& l = level(ctx, p.L);
+  const EvkGenConst gc = evk_gen_const(p, ev);
+  uint32_t key[8];
+  stream_key(ctx, key);
   const size_t words = 2ull * ev.dnum * (p.L + ev.kP) * p.N;
   void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, evk_scratch_bytes(p.L, ev.kP, p.N));
   uint64_t* evk_d = nullptr;
@@ -859,6 +870,119 @@ int shelfi_dev_add(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev
       if (out_dev != in && overlaps(in, out_dev, words))
         throw Error{SHELFI_ERR_ARG, "EvalAdd output must be an input exactly or not overlap the inputs"};
     launch_ct_add(a_dev, b_dev, K * 2 * towers, towers, p.logN, ctx->dt.tc, out_dev, (hipStream_t)stream);
+  });
+}
+
+}  // extern "C"
+
+// ---- multiparty evaluation keys (mkhe.cpp:271-317; multikey.hip) ----
+namespace shelfi {
+namespace {
+struct DevWords {  // a device buffer of uint64 words, freed on scope exit
+  uint64_t* p = nullptr;
+  explicit DevWords(size_t words) { SHELFI_HIP(hipMalloc((void**)&p, (words ? words : 1) * 8)); }
+  ~DevWords() { (void)hipFree(p); }
+  DevWords(const DevWords&) = delete;
+  DevWords& operator=(const DevWords&) = delete;
+};
+
+// the calls' device flag (dev_flag[7]): zeroed on the stream before the kernels, read back with the
+// result before the call's one synchronisation
+uint32_t* mk_flag_reset(shelfi_ctx* ctx) {
+  uint32_t* flag = ctx->dev_flag + 7;
+  SHELFI_HIP(hipMemsetAsync(flag, 0, 4, ctx->stream));
+  return flag;
+}
+
+// result and flag back, one synchronisation; a raised flag refuses the call and leaves `out` untouched
+void mk_finish(shelfi_ctx* ctx, const uint64_t* out_dev, size_t words, uint64_t* out) {
+  std::vector<uint64_t> host(words);
+  SHELFI_HIP(hipMemcpyAsync(ctx->host_flag + 7, ctx->dev_flag + 7, 4, hipMemcpyDeviceToHost, ctx->stream));
+  SHELFI_HIP(hipMemcpyAsync(host.data(), out_dev, words * 8, hipMemcpyDeviceToHost, ctx->stream));
+  SHELFI_HIP(hipStreamSynchronize(ctx->stream));
+  const uint32_t f = ctx->host_flag[7];
+  if (f & kMkBadResidue) throw Error{SHELFI_ERR_ARG, "multiparty key: a residue is >= its tower's modulus"};
+  if (f & kMkADiffers)
+    throw Error{SHELFI_ERR_ARG, "multiparty key: the keys' a-vectors differ (shares of different lead keys)"};
+  std::memcpy(out, host.data(), words * 8);
+}
+}  // namespace
+}  // namespace shelfi
+
+extern "C" {
+
+int shelfi_multi_key_switch_gen(shelfi_ctx* ctx, int32_t index, const uint64_t* prev, uint64_t* out) {
+  if (!ctx || !out) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    require_keys(ctx);
+    DeviceGuard dg(ctx->device);
+    const Params& p = ctx->p;
+    const uint32_t galois = index ? rotation_galois(ctx, index) : 1;  // 1: s' = s, the EvalMult share
+    EvalState& ev = eval_state(ctx);
+    LevelState& l = level(ctx, p.L);
+    const EvkGenConst gc = evk_gen_const(p, ev);
+    const size_t words = 2ull * ev.dnum * (p.L + ev.kP) * p.N;
+    void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, evk_scratch_bytes(p.L, ev.kP, p.N));
+    DevWords out_d(words), prev_d(prev ? words : 0);
+    if (prev) SHELFI_HIP(hipMemcpyAsync(prev_d.p, prev, words * 8, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t key[8];
+    stream_key(ctx, key);
+    uint32_t* flag = mk_flag_reset(ctx);
+    launch_mk_share(gc, ctx->dt, l.ext, ctx->dt.cdt, ctx->dt.cdt_len, key, ctx->dk.sk, galois,
+                    prev ? prev_d.p : nullptr, out_d.p, scratch, flag, ctx->stream);
+    std::memset(key, 0, sizeof(key));
+    mk_finish(ctx, out_d.p, words, out);
+  });
+}
+
+int shelfi_multi_add_eval_keys(shelfi_ctx* ctx, const uint64_t* const* keys, size_t n, int sum_a, uint64_t* out) {
+  if (!ctx || !out || !keys) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    if (n < 1 || n > (size_t)kMkMaxKeys) throw Error{SHELFI_ERR_ARG, "multiparty key add takes 1..16 keys"};
+    for (size_t i = 0; i < n; ++i)
+      if (!keys[i]) throw Error{SHELFI_ERR_ARG, "multiparty key add: null key"};
+    DeviceGuard dg(ctx->device);
+    const Params& p = ctx->p;
+    EvalState& ev = eval_state(ctx);
+    LevelState& l = level(ctx, p.L);
+    const EvkGenConst gc = evk_gen_const(p, ev);
+    const size_t words = 2ull * ev.dnum * (p.L + ev.kP) * p.N;
+    DevWords in_d(words * n), out_d(words);
+    MkKeys mk{};
+    mk.n = (uint32_t)n;
+    for (size_t i = 0; i < n; ++i) {
+      mk.k[i] = in_d.p + i * words;
+      SHELFI_HIP(hipMemcpyAsync(in_d.p + i * words, keys[i], words * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    uint32_t* flag = mk_flag_reset(ctx);
+    launch_mk_key_add(mk, gc, l.ext.tc, sum_a != 0, flag, out_d.p, ctx->stream);
+    mk_finish(ctx, out_d.p, words, out);
+  });
+}
+
+int shelfi_multi_mult_eval_key(shelfi_ctx* ctx, const uint64_t* joint, uint64_t* out) {
+  if (!ctx || !out || !joint) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    require_keys(ctx);
+    DeviceGuard dg(ctx->device);
+    const Params& p = ctx->p;
+    EvalState& ev = eval_state(ctx);
+    LevelState& l = level(ctx, p.L);
+    const EvkGenConst gc = evk_gen_const(p, ev);
+    const size_t words = 2ull * ev.dnum * (p.L + ev.kP) * p.N;
+    void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, evk_scratch_bytes(p.L, ev.kP, p.N));
+    DevWords joint_d(words), out_d(words);
+    SHELFI_HIP(hipMemcpyAsync(joint_d.p, joint, words * 8, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t key[8];
+    stream_key(ctx, key);
+    uint32_t* flag = mk_flag_reset(ctx);
+    launch_mk_round2(gc, ctx->dt, l.ext, ctx->dt.cdt, ctx->dt.cdt_len, key, ctx->dk.sk, joint_d.p, out_d.p, scratch,
+                     flag, ctx->stream);
+    std::memset(key, 0, sizeof(key));
+    mk_finish(ctx, out_d.p, words, out);
   });
 }
 

@@ -812,6 +812,31 @@ size_t evk_scratch_bytes(uint32_t L, uint32_t kP, uint32_t N) {
   return (uint64_t)N * 8 * (2ull * (L + kP) + kP + 1) + 64;  // e | a | s over P | s0
 }
 
+// s over the special primes in EVALUATION: sp [kP][N] from tower 0 of sk (s0 [N]: scratch)
+void launch_evk_s_ext(const EvkGenConst& g, const DeviceTables& dtq, const DeviceTables& dte, const uint64_t* sk,
+                      uint64_t* sp, uint64_t* s0, hipStream_t s) {
+  const uint32_t N = 1u << g.logN;
+  SHELFI_HIP(hipMemcpyAsync(s0, sk, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
+  launch_ntt(s0, 1, 1, g.logN, true, dtq, s);  // tower 0 of s -> COEFFICIENT
+  const uint64_t kpn = (uint64_t)g.kP * N;
+  hipLaunchKernelGGL(evk_s_ext_kernel, dim3((uint32_t)((kpn + 255) / 256)), dim3(256), 0, s, s0, g.q0, g.logN,
+                     g.kP, dte.tc + g.L, sp);
+  SHELFI_HIP(hipGetLastError());
+  launch_ntt(sp, g.kP, g.kP, g.logN, false, tower_view(dte, g.L, N), s);
+}
+
+// digit j's (e_j, a_j) in COEFFICIENT / uniform form under a nonce base (evk_sample_kernel)
+void launch_evk_sample(const EvkGenConst& g, const DeviceTables& dte, const uint64_t* cdt, int cdt_len,
+                       const uint32_t key[8], uint64_t nonce_base, uint32_t j, uint64_t* eb, uint64_t* ab,
+                       hipStream_t s) {
+  const uint32_t N = 1u << g.logN, T0 = g.L + g.kP;
+  Key8 k8;
+  for (int i = 0; i < 8; ++i) k8.k[i] = key[i];
+  hipLaunchKernelGGL(evk_sample_kernel, dim3((N / 8 + 255) / 256), dim3(256), 0, s, g.logN, T0, dte.tc, cdt,
+                     cdt_len, k8, nonce_base, j, eb, ab);
+  SHELFI_HIP(hipGetLastError());
+}
+
 void launch_evk_keygen(const EvkGenConst& g, const DeviceTables& dtq, const DeviceTables& dte,
                        const uint64_t* cdt, int cdt_len, const uint32_t key[8], const uint64_t* sk,
                        uint64_t* evk, void* scratch, hipStream_t s, uint32_t galois) {
@@ -821,20 +846,10 @@ void launch_evk_keygen(const EvkGenConst& g, const DeviceTables& dtq, const Devi
   uint64_t* ab = eb + (uint64_t)T0 * N;
   uint64_t* sp = ab + (uint64_t)T0 * N;
   uint64_t* s0 = sp + (uint64_t)g.kP * N;
-  Key8 k8;
-  for (int i = 0; i < 8; ++i) k8.k[i] = key[i];
-  SHELFI_HIP(hipMemcpyAsync(s0, sk, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
-  launch_ntt(s0, 1, 1, g.logN, true, dtq, s);  // tower 0 of s -> COEFFICIENT
-  const uint64_t kpn = (uint64_t)g.kP * N;
-  hipLaunchKernelGGL(evk_s_ext_kernel, dim3((uint32_t)((kpn + 255) / 256)), dim3(256), 0, s, s0, g.q0, g.logN,
-                     g.kP, dte.tc + g.L, sp);
-  SHELFI_HIP(hipGetLastError());
-  launch_ntt(sp, g.kP, g.kP, g.logN, false, tower_view(dte, g.L, N), s);
+  launch_evk_s_ext(g, dtq, dte, sk, sp, s0, s);
   const uint64_t tn = (uint64_t)T0 * N;
   for (uint32_t j = 0; j < g.dnum; ++j) {
-    hipLaunchKernelGGL(evk_sample_kernel, dim3((N / 8 + 255) / 256), dim3(256), 0, s, g.logN, T0, dte.tc, cdt,
-                       cdt_len, k8, nonce_base, j, eb, ab);
-    SHELFI_HIP(hipGetLastError());
+    launch_evk_sample(g, dte, cdt, cdt_len, key, nonce_base, j, eb, ab, s);
     launch_ntt(eb, T0, T0, g.logN, false, dte, s);
     hipLaunchKernelGGL(evk_combine_kernel, dim3((uint32_t)((tn + 255) / 256)), dim3(256), 0, s, eb, ab, sk, sp,
                        dte.tc, g, galois, j, evk);

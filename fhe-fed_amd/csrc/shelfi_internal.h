@@ -252,6 +252,7 @@ struct shelfi_ctx {
                                  // [2] max decode logError (noise flooding), [3] bytes-API
                                  // upload residue >= q, [4] arena upload residue >= q, [5] the
                                  // packed wire's pack check, [6] shelfi_dev_check_residues,
+                                 // [7] the multiparty key calls (kMkBadResidue | kMkADiffers),
                                  // (round 6: the encode and decode-CRT range flags are GenFlag words)
   // arena slots whose last upload was refused (shelfi_dev_arena_put*): an aggregation
   // over an arena range holding one fails instead of summing the refused residues
@@ -509,5 +510,37 @@ size_t evk_scratch_bytes(uint32_t L, uint32_t kP, uint32_t N);
 void launch_evk_keygen(const EvkGenConst& g, const DeviceTables& dtq, const DeviceTables& dte,
                        const uint64_t* cdt, int cdt_len, const uint32_t key[8], const uint64_t* sk,
                        uint64_t* evk, void* scratch, hipStream_t s, uint32_t galois = 0);
+// its two first steps, shared with the multiparty key protocols: s over the special primes
+// (sp [kP][N] EVALUATION; s0 [N] scratch), and digit j's (e_j, a_j) draw under a nonce base
+void launch_evk_s_ext(const EvkGenConst& g, const DeviceTables& dtq, const DeviceTables& dte, const uint64_t* sk,
+                      uint64_t* sp, uint64_t* s0, hipStream_t s);
+void launch_evk_sample(const EvkGenConst& g, const DeviceTables& dte, const uint64_t* cdt, int cdt_len,
+                       const uint32_t key[8], uint64_t nonce_base, uint32_t j, uint64_t* eb, uint64_t* ab,
+                       hipStream_t s);
+
+// ---- multiparty evaluation keys for threshold CKKS (multikey.hip; mkhe.cpp:271-317) ----
+// Keys are [2][dnum][L + kP][N] on the device; scratch = evk_scratch_bytes(L, kP, N).  *flag (zeroed
+// by the caller) takes kMkBadResidue when an imported word is >= its tower's modulus, kMkADiffers
+// when the a-vectors of the keys to add differ.
+constexpr uint32_t kMkBadResidue = 1, kMkADiffers = 2;
+constexpr int kMkMaxKeys = 16;  // uint64 sums of 16 residues below 2^60 cannot wrap
+struct MkKeys {
+  const uint64_t* k[kMkMaxKeys];
+  uint32_t n;
+};
+// Round 1 (MultiKeySwitchGen / MultiEvalSumKeyGen): b_j = NTT(e_j) - a_j s + [digit j] P s', s' = s
+// (galois = 1, the EvalMult share) or sigma_g(s); a_j drawn (prev = null, the lead party) or copied
+// from prev's a-vector.  Nonce domain (7 << 56) | (galois << 24).
+void launch_mk_share(const EvkGenConst& g, const DeviceTables& dtq, const DeviceTables& dte, const uint64_t* cdt,
+                     int cdt_len, const uint32_t key[8], const uint64_t* sk, uint32_t galois,
+                     const uint64_t* prev, uint64_t* out, void* scratch, uint32_t* flag, hipStream_t s);
+// Round 2 (MultiMultEvalKey): out[v][j] = joint[v][j] s + NTT(E_{v,j}); nonce (8 << 56) | (v << 24) | (j << 16)
+void launch_mk_round2(const EvkGenConst& g, const DeviceTables& dtq, const DeviceTables& dte, const uint64_t* cdt,
+                      int cdt_len, const uint32_t key[8], const uint64_t* sk, const uint64_t* joint,
+                      uint64_t* out, void* scratch, uint32_t* flag, hipStream_t s);
+// MultiAddEvalKeys / MultiAddEvalSumKeys (sum_a = false: a-vectors compared, the first one kept) and
+// MultiAddEvalMultKeys (sum_a: both vectors summed) over k.n keys
+void launch_mk_key_add(const MkKeys& k, const EvkGenConst& g, const TowerConst* te, bool sum_a, uint32_t* flag,
+                       uint64_t* out, hipStream_t s);
 
 }  // namespace shelfi

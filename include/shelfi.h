@@ -498,6 +498,31 @@ int shelfi_partial_blob_pack(uint32_t ring_dim, uint32_t num_towers, uint32_t ba
                              uint32_t depth, double scale, uint64_t params_id, uint64_t key_id, int lead,
                              const uint64_t* residues, uint8_t** out, size_t* out_len);
 
+/* ---- multiparty evaluation keys for threshold CKKS (mkhe.cpp:271-317) ---- *
+ * The parties make the joint EvalMult, rotation and EvalSum keys of s = sum s_i without anybody
+ * holding s.  Keys are host arrays of shelfi_eval_key_words words, [2][dnum][L + num_special][N]
+ * (b-vector, a-vector), EVALUATION.  These calls install nothing: the joint keys go to
+ * shelfi_set_eval_key / shelfi_set_rotation_key.  Common answers: no key pair SHELFI_ERR_STATE; a
+ * chain with num_towers + special primes > 16, a word >= its tower's modulus in an imported key,
+ * NULL ctx / out: SHELFI_ERR_ARG. */
+/* Round 1, one party's share: b_j = NTT(e_j) - a_j s_i + [digit j] P s'_i.  index = 0: the EvalMult
+ * share, s' = s_i -- cc->KeySwitchGen(sk, sk) (mkhe.cpp:271) for the lead party, cc->MultiKeySwitchGen
+ * (mkhe.cpp:296) for the others.  index != 0 (|index| < batch): the rotation share of that index,
+ * s' = sigma_g(s_i) -- one index of cc->MultiEvalSumKeyGen (mkhe.cpp:284; cc->EvalSumKeyGen, :274, for
+ * the lead).  prev = NULL: the lead party draws a_j; otherwise a_j is copied from prev's a-vector.
+ * Stream: the context's ChaCha20 key, nonce (7 << 56) | (g << 24) | (digit << 16) | (1 + tower) (tower
+ * field 0 for e_j; g = 1 for index 0). */
+int shelfi_multi_key_switch_gen(shelfi_ctx* ctx, int32_t index, const uint64_t* prev, uint64_t* out);
+/* The sum of n (1..16) keys mod q_t.  sum_a = 0: cc->MultiAddEvalKeys (mkhe.cpp:298) /
+ * cc->MultiAddEvalSumKeys (mkhe.cpp:288) -- the b-vectors are summed, the a-vectors must be identical
+ * (else SHELFI_ERR_ARG) and are kept.  sum_a = 1: cc->MultiAddEvalMultKeys (mkhe.cpp:314) -- both
+ * vectors are summed.  Needs no keys. */
+int shelfi_multi_add_eval_keys(shelfi_ctx* ctx, const uint64_t* const* keys, size_t n, int sum_a, uint64_t* out);
+/* Round 2 of the EvalMult key, cc->MultiMultEvalKey(joint, sk_i) (mkhe.cpp:307, :311): out = (b_j s_i +
+ * NTT(E2_j), a_j s_i + NTT(E1_j)); the sum of every party's answer with sum_a = 1 is the EvalMult key
+ * of s.  Stream: nonce (8 << 56) | (vector << 24) | (digit << 16). */
+int shelfi_multi_mult_eval_key(shelfi_ctx* ctx, const uint64_t* joint, uint64_t* out);
+
 /* ---- test hooks (host-visible tables) ------------------------------------- */
 /* CKKS special-FFT twiddles (flat, index lenh + j) as used by the kernels. */
 int shelfi_fft_twiddles(uint32_t slots, double* inv_re, double* inv_im, double* fwd_re,
