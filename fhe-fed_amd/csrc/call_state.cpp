@@ -52,7 +52,7 @@ bool gen_flag_raised(const shelfi_ctx* ctx, const GenFlag& f, int w) {
   return __atomic_load_n(ctx->map_flag_host + w, __ATOMIC_ACQUIRE) == f.gen;
 }
 
-// The encode range flag of an encrypt call (kernels.hip enc_range_flag): non-finite values are refused;
+// The encode range flag of an encrypt call (encrypt.hip enc_range_flag): non-finite values are refused;
 // a finite message coefficient above 2^61 in magnitude means the call is redone on the large-value path
 // (the callers count that in ctx->encode_redo_count).
 bool encode_needs_approx(const shelfi_ctx* ctx, const GenFlag& f) {

@@ -5,7 +5,7 @@
 // Why this is exact: each rank's partial is sum_{c in rank} W_c ct_c mod q_t, a residue
 // below q_t < 2^60; a uint64 sum of W <= 16 of them stays below 2^64, and EvalAdd is
 // order-independent, so RCCL's reduction order (ring, tree) cannot change the result.
-// The fold back into [0, q_t) is launch_modq (kernels.hip).
+// The fold back into [0, q_t) is launch_modq (wavg.hip).
 //
 // RCCL is opened with dlopen(RTLD_LOCAL | RTLD_DEEPBIND) on first use, from the ROCm
 // install this library's HIP runtime comes from: a PyTorch process already carries its

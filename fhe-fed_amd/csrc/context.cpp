@@ -9,7 +9,7 @@
 //   shelfi_decrypt           <- CKKS::decrypt                   (ckks.cpp:170-213)  bytes_api.cpp
 //   shelfi_weighted_average  <- CKKS::computeWeightedAverage    (ckks.cpp:264-320)  bytes_api.cpp
 // Host code only validates, moves bytes and precomputes constant tables; every per-ciphertext
-// operation is a kernel in kernels.hip.
+// operation is a kernel in one of the .hip files.
 #include <sys/random.h>
 
 #include <cmath>

@@ -1,6 +1,14 @@
-// dev_common.h — device helpers shared by the gfx950 kernel files (kernels.hip,
-// keyswitch.hip): 64-bit modular arithmetic (Shoup, lazy butterflies, borrow-free
-// reductions), complex f64 helpers and the ChaCha20 / Gaussian / ternary samplers.
+// dev_common.h — device helpers shared by the hand-written gfx950 kernel files of the RNS-CKKS
+// aggregation path (the .hip files of this directory): 64-bit modular arithmetic (Shoup, lazy
+// butterflies, borrow-free reductions), complex f64 helpers and the ChaCha20 / Gaussian / ternary samplers.
+//
+// Data layout in HBM (all uint64 residues, EVALUATION domain, PALISADE's
+// bit-reversed order):  ciphertext batch [K][2][L][N]  (ct, poly, tower, coeff) —
+// the order of a serialized vector<Ciphertext<DCRTPoly>> (ckks.cpp:98-100).
+//
+// 64-bit modular arithmetic: CDNA4 has no 64x64->128 multiply; products are
+// built from v_mad_u64_u32 / v_mul_hi_u32 by the compiler (__umul64hi).  Constant
+// multiplications use Shoup's precomputed quotient (w' = floor(w 2^64 / q)).
 #pragma once
 
 #include <hip/hip_runtime.h>

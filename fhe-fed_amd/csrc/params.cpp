@@ -4,7 +4,7 @@
 // (genCryptoContextCKKS(multDepth, scaleFactorBits, batchSize)): the EXACTRESCALE
 // modulus chain, minimal primitive 2N-th roots and the HE-standard ring dimension.
 // These are one-time setup computations on the host; every per-ciphertext
-// operation runs in kernels.hip.
+// operation runs in the .hip files.
 #include <algorithm>
 #include <cmath>
 #include <cstring>

@@ -168,7 +168,7 @@ struct DeviceTables {
   // [L][kEncTab]: the radix-4 outputs of 4 ternary inputs (stages 0-1, 4 x 81) and W0 e for e1's
   // stage 0 (e + 64, |e| <= 63), all canonical
   uint64_t* enc_tab = nullptr;
-  // encrypt's NTT(v) without the columns pass (round 5, kernels.hip ntt_fwd_blocks_enc_pp<VT>): for a
+  // encrypt's NTT(v) without the columns pass (round 5, encrypt.hip ntt_fwd_blocks_enc_pp<VT>): for a
   // 16-row columns pass (logN - BL = 4), [L][16 rows][4 groups][81]: output row r of the 4 column
   // stages applied to v restricted to rows g, g + 4, g + 8, g + 12 with ternary pattern p (base 3),
   // canonical; the row's value is the sum over the 4 groups.  nullptr for other shapes.
@@ -302,7 +302,7 @@ struct shelfi_ctx {
 
 namespace shelfi {
 
-// device-side launchers (kernels.hip)
+// device-side launchers (the .hip files)
 constexpr int kWavgMaxLearners = 16;  // per launch (limb sums stay < 2^64)
 constexpr int kArenaChunk = 512;      // residues per (row, learner) slice of an arena
 struct WavgArgs {
@@ -319,7 +319,7 @@ void launch_wavg(const WavgArgs& a, const TowerConst* tc, hipStream_t s);
 // bits + the top bit in a flag plane), else 4 ceil(bitlength(q_t) / 4); at least 32, at most 60.
 // Rows of 512 residues of one (ct, poly, tower) in natural order, each row holding the C learners'
 // slices side by side, a slice 16 U_t dwords (lane l of a wave owns residues 2l, 2l + 1 (+128 g,
-// g < 4), packed into 16-byte / 8-byte / 4-byte field planes and a byte flag plane, see kernels.hip).
+// g < 4), packed into 16-byte / 8-byte / 4-byte field planes and a byte flag plane, see wavg.hip).
 struct ArenaPack {
   uint32_t w[kMaxTowers];    // U_t
   uint32_t pre[kMaxTowers];  // sum of U_t' for t' < t
@@ -361,6 +361,31 @@ void launch_ntt(uint64_t* polys, uint64_t P, uint32_t L, uint32_t logN, bool inv
                 const DeviceTables& dt, hipStream_t s);
 void launch_ntt_cols(uint64_t* polys, uint64_t P, uint32_t L, uint32_t logN, bool inverse,
                      const DeviceTables& dt, hipStream_t s);
+// Host side of xcd_block: the combo count G when the block passes may deal (tower, block)
+// combos per XCD (G % 8 == 0), else 0.  SHELFI_XCD_ORDER=0 keeps the natural order (A/B
+// probe switch).
+inline uint32_t xcd_combos(uint64_t G) {
+  if (!switches().xcd_order) return 0;
+  return (G % 8 == 0 && G <= 0xFFFFFFFFull) ? (uint32_t)G : 0;
+}
+// Wave-local exchanges in the persistent block passes (the default since round 4; SHELFI_NTT_WL=0
+// keeps the four-barrier form): bit-identical, decrypt 2-3% and flooded decrypt ~2% faster, encrypt
+// within 1% (profiles/r04r/wl_ab*.txt).
+inline bool ntt_wave_local() { return switches().ntt_wl; }
+// Workgroups of the persistent decrypt / encrypt block passes: LDS-bound residency per CU
+// times the CUs, spread evenly over the (tower, block) combos (at least one each).
+inline uint32_t pp_per_combo(uint32_t ncombo, uint64_t K, uint32_t per_cu) {
+  static const uint32_t cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    return (uint32_t)n;
+  }();
+  uint64_t pc = (uint64_t)cus * per_cu / ncombo;
+  if (pc < 1) pc = 1;
+  if (pc > K) pc = K;
+  return (uint32_t)pc;
+}
 // A flag in pinned host memory the kernels write directly (round 6): word i holds the generation of the
 // last call that raised it, so a call compares it with its own generation after its one synchronisation --
 // no reset before a call and no readback copy after it (each was a ~2-4 us copy-engine op plus its launch
@@ -376,7 +401,7 @@ void launch_encrypt(const Params& p, const DeviceTables& dt, const DeviceKeys& d
                     const double* x, uint64_t n, uint64_t K, uint64_t* ct, void* scratch,
                     const uint32_t key[8], uint64_t g0, GenFlag flag, hipStream_t s);
 // encode's large-value path (|x Delta| > 2^61 somewhere in the call; PALISADE's approxFactor): the
-// same ciphertexts' encryption redone with per-ciphertext scale-down exponents (kernels.hip)
+// same ciphertexts' encryption redone with per-ciphertext scale-down exponents (encrypt.hip)
 void launch_encrypt_approx(const Params& p, const DeviceTables& dt, const DeviceKeys& dk, const double* x,
                            uint64_t n, uint64_t K, uint64_t* ct, void* scratch, const uint32_t key[8],
                            uint64_t g0, hipStream_t s);
@@ -412,7 +437,7 @@ size_t decrypt_scratch_bytes(const Params& p, uint64_t K);
 void launch_keygen(const Params& p, const DeviceTables& dt, const uint32_t key[8], uint64_t* sk,
                    uint64_t* pk, void* scratch, hipStream_t s);
 size_t keygen_scratch_bytes(const Params& p);
-// threshold key chain step (kernels.hip): prev_pk [2][L][N] (b, a) on the device -> sk, pk
+// threshold key chain step (keygen.hip): prev_pk [2][L][N] (b, a) on the device -> sk, pk
 void launch_keygen_chain(const Params& p, const DeviceTables& dt, const uint32_t key[8], const uint64_t* prev_pk,
                          uint64_t* sk, uint64_t* pk, void* scratch, hipStream_t s);
 size_t keygen_chain_scratch_bytes(const Params& p);

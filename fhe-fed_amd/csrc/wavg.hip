@@ -5,7 +5,7 @@
 //   arena_pack_kernel  a learner's upload into its packed slices + the residue check
 //   blob_{un}pack      the packed wire format (C = 1 slices)
 //   modq_kernel        fold a collective's uint64 sum of partials back to [0, q)
-// Split out of kernels.hip in round 4 (the NTT / FFT / encrypt / decrypt kernels stay there).
+// (The NTT, encrypt, decrypt and keygen kernels: ntt.hip, encrypt.hip, decrypt.hip, keygen.hip.)
 #include <hip/hip_runtime.h>
 
 #include <type_traits>

@@ -1,4 +1,4 @@
-"""numpy restatement of the packed arena's documented layout (kernels.hip 'packed
+"""numpy restatement of the packed arena's documented layout (wavg.hip 'packed
 arena'): the width rule of arena_pack (dev_api.cpp) and the row / slice / plane geometry of
 arena_pack_kernel and wavg_packed.  Test infrastructure: the GPU test compares the device arena's
 words with pack_arena(); the CPU test round-trips pack_arena() / unpack_arena()."""

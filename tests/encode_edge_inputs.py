@@ -2,7 +2,7 @@
 edges of their range, for tests/test_encode_edge_inputs.py (CPU: every builder lands where it claims,
 judged by the oracle) and tests/test_gpu_encode_edge.py (the HIP encrypt on every dispatch branch).
 
-The ranges (fhe-fed_amd/csrc/kernels.hip, "encode's large-value path"; oracle/ckks_oracle.c
+The ranges (fhe-fed_amd/csrc/encrypt.hip, "encode's large-value path"; oracle/ckks_oracle.c
 or_encode_coeffs_ex):
   |m| <= 2^61                  the fast kernels; nothing is flagged
   2^61 < |m| <= 2^62 - 512     the call is redone (launch_encrypt_approx) with logApprox = 0

@@ -1,7 +1,7 @@
 """The arithmetic behind decrypt's tower prefix and binary32 CRT quotient,
 checked on the CPU with Python integers against the oracle's exact centred CRT.
 
-The kernel (`crt_value`, kernels.hip) decodes with the shortest prefix of q_0.. whose product Q'
+The kernel (`crt_value`, decrypt.hip) decodes with the shortest prefix of q_0.. whose product Q'
 exceeds 2^130 (`decode_towers`, call_state.cpp): y_t = r_t (Q'/q_t)^-1 mod q_t, k = round(sum_t y_t / q_t)
 from binary32 terms (y_t >> s_t) * (2^s_t / q_t) (s_t = max(0, bitlen(q_t) - 32)), and
 X = sum_t y_t (Q'/q_t) - k Q' mod 2^128 read as a signed 128-bit integer.  For every |X| < 2^127

@@ -1,5 +1,5 @@
 """Encrypt at the edges of its message-coefficient range, on every dispatch branch of launch_encrypt
-(fhe-fed_amd/csrc/kernels.hip).  The inputs are tests/encode_edge_inputs.py's; that they land where
+(fhe-fed_amd/csrc/encrypt.hip).  The inputs are tests/encode_edge_inputs.py's; that they land where
 they claim (coefficients in (2^60, 2^61], exactly 2^61, 2^61 + 512, 2^62 - 512, the wrap, logApprox 1,
 logApprox ~950, an infinite scaled value) is checked on the CPU in tests/test_encode_edge_inputs.py,
 together with the decode's closeness to x.  Here every case asserts only equalities:

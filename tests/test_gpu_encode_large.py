@@ -2,7 +2,7 @@
 CKKSPackedEncoding::Encode's approxFactor, SURVEY App. B.2): values whose message coefficients
 round(FFTSpecialInv(x)_i / S * Delta) exceed 2^61 are no longer refused.  The fast kernels flag such a
 coefficient (not |x Delta|: uniform data of amplitude xmax has coefficients near xmax Delta / sqrt(S)
-times a few), and the call is redone with per-ciphertext scale-down exponents (kernels.hip
+times a few), and the call is redone with per-ciphertext scale-down exponents (encrypt.hip
 launch_encrypt_approx); CKKS.encode_redo_count() says whether it was.  Every ciphertext is bit-exact vs
 the oracle's restatement (or_encode_coeffs_ex), and decrypts within 2^-40 relative of the input.
 tests/test_gpu_encode_edge.py walks the range's edges on every dispatch branch.

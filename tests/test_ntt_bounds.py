@@ -1,7 +1,8 @@
 """Bound bookkeeping of the lazy inverse (GS) NTT passes, restated on the host.
 
-The compile-time passes (csrc/kernels.hip: inv_chunk_ct in ntt_inv_blocks_dec_ct, ntt_inv_cols,
-ntt_inv_cols_crt; csrc/dev_common.h: gs_bfly_b, gs_in8) keep residues unreduced between stages. With
+The compile-time passes (csrc/transform_dev.h: inv_chunk_ct; csrc/decrypt.hip: ntt_inv_blocks_dec_ct,
+ntt_inv_cols_crt; csrc/ntt.hip: ntt_inv_cols; csrc/dev_common.h: gs_bfly_b, gs_in8) keep residues
+unreduced between stages. With
 q < 2^60 every intermediate must stay below 16q <= 2^64. This walks the same schedule element by
 element with worst-case bounds (in units of q) and checks that it never reaches 16q, that the blocks
 pass hands the columns pass values below 8q, and that the bit-exactness tests' assumption (outputs of

@@ -1,6 +1,7 @@
 """Per-kernel instruction counts from `make -C fhe-fed_amd/csrc asm` output.
 
-usage: python tools/isa_count.py build/kernels.s [substring ...]
+usage: python tools/isa_count.py build/ntt.s [build/encrypt.s build/decrypt.s build/keygen.s ...] [substring ...]
+(one .s file per .hip file; arguments ending in .s are files, the rest substrings)
 Prints static VALU / 64-bit mad / mul_lo / mul_hi / LDS / VGPR counts per kernel whose
 mangled name contains every substring (static counts: a proxy for the issue work
 of the fully unrolled NTT kernels)."""
@@ -20,8 +21,9 @@ def kernels(path):
 
 
 def main():
-    path, subs = sys.argv[1], sys.argv[2:]
-    for name, body, vg in kernels(path):
+    paths = [a for a in sys.argv[1:] if a.endswith(".s")]
+    subs = [a for a in sys.argv[1:] if not a.endswith(".s")]
+    for name, body, vg in (k for path in paths for k in kernels(path)):
         if not all(x in name for x in subs):
             continue
         c = lambda pat: len(re.findall(pat, body, re.M))

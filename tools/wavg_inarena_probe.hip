@@ -1,7 +1,7 @@
 // Probe: does writing the weighted sum into an extra slot of the interleaved arena
 // (reads and the write of a block in one contiguous (C+1) x 4 KiB region) make the
 // wavg launch less sensitive to physical placement than a separate output buffer?
-// Same kernel body as wavg_kernel<true> (kernels.hip); the only difference is where
+// Same kernel body as wavg_kernel<true> (wavg.hip); the only difference is where
 // each block's 4 KiB of output goes.  Alternates the two layouts A/B in one process,
 // over several fresh allocations.
 //   hipcc -O3 --offload-arch=gfx950 -o tools/build/wavg_inarena tools/wavg_inarena_probe.hip

@@ -1,6 +1,6 @@
 // wavg_variants.hip — experiment harness (not product code): variants of the wavg
 // kernel and a compute-free streaming ceiling, timed interleaved in one process by
-// tools/wavg_variants.py.  Same math as fhe-fed_amd/csrc/kernels.hip wavg_kernel.
+// tools/wavg_variants.py.  Same math as fhe-fed_amd/csrc/wavg.hip wavg_kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
