@@ -181,3 +181,101 @@ def protocol(seeds, sks, q, psi, indices=()):
             rs.append(share(sd, sk, q, psi, r, rs[-1] if rs else None))
         rot[r] = key_add(rs, q, N)
     return final, rot, mid
+
+
+# ---- helpers of tests/test_gpu_multikey_edges.py (held to their meaning by tests/test_multikey_ref.py) ----
+def ext_moduli(N, q):
+    """The moduli of Q then of P, uint64 [L + kP]."""
+    _, _, p, _ = O.special_primes(N, q)
+    return np.array([int(v) for v in q] + [int(v) for v in p], np.uint64)
+
+
+def uniform_key(rng, mods, dn, N):
+    """A key [2][dnum][T][N] of residues uniform below each tower's modulus."""
+    out = np.empty((2, dn, len(mods), N), np.uint64)
+    for t, mt in enumerate(mods):
+        out[:, :, t] = rng.integers(0, int(mt), size=(2, dn, N), dtype=np.uint64)
+    return out
+
+
+def full_key(mods, dn, N):
+    """A key whose every word is q_t - 1."""
+    out = np.empty((2, dn, len(mods), N), np.uint64)
+    out[:] = (np.asarray(mods, np.uint64) - np.uint64(1))[None, None, :, None]
+    return out
+
+
+def chain_step(seed, prev_pk, q, psi):
+    """MultipartyKeyGen(prev_pk) under `seed`: -> (pk, sk) with sk = NTT(s), pk = (prev.b + NTT(e) -
+    prev.a sk, prev.a); s, e the oracle's keygen draw of that seed (its uniform a unused)."""
+    prev = np.asarray(prev_pk, np.uint64)
+    N = prev.shape[-1]
+    s, e, _ = O.sample_keygen(seed, N, q)
+    sk, pk = np.empty((len(q), N), np.uint64), np.empty((2, len(q), N), np.uint64)
+    for t, (qt, pt) in enumerate(zip(q, psi)):
+        m = np.uint64(qt)
+        sk[t] = O.ntt_fwd((s % int(qt)).astype(np.uint64), qt, pt)
+        ne = O.ntt_fwd((e % int(qt)).astype(np.uint64), qt, pt)
+        pk[0, t] = (prev[0, t] + (ne + m - R.mulmod(prev[1, t], sk[t], m)) % m) % m
+        pk[1, t] = prev[1, t]
+    return pk, sk
+
+
+def share_terms(seed, sk, q, psi, index=0):
+    """What a follower's share holds besides prev: (C [dnum][T][N], S [T][N], mods) with C = NTT(e_j) +
+    [t in digit j] (P mod q_t) s'; share(..., prev) = (C - prev.a S, prev.a).  For sweeps over many prev
+    keys of one (seed, index): the NTTs are done once."""
+    N, L, dn, al, T = _dims(sk, q)
+    key = O.seed_to_key(seed)
+    S, mods, roots = R.s_ext(sk, q, psi)
+    g = 1 if index == 0 else R.galois(N, index)
+    sp = S[:L] if g == 1 else R.sigma_eval(S[:L], g, q, psi)
+    pm = R.p_mod(q, N)
+    Cc = np.empty((dn, T, N), np.uint64)
+    for j in range(dn):
+        e, _ = sample_digit(key, (7 << 56) | (g << 24), j, N, mods, with_a=False)
+        Cc[j] = _ntt_small(e, mods, roots)
+        for t in range(j * al, min(L, (j + 1) * al)):
+            m = np.uint64(mods[t])
+            Cc[j, t] = (Cc[j, t] + R.mulmod(np.uint64(pm[t]), sp[t], m)) % m
+    return Cc, S, mods
+
+
+def share_from_terms(terms, prev):
+    """share(seed, sk, q, psi, index, prev) from share_terms(seed, sk, q, psi, index)."""
+    Cc, S, mods = terms
+    a = np.asarray(prev, np.uint64)[1]
+    out = np.empty((2,) + a.shape, np.uint64)
+    for t, mt in enumerate(mods):
+        m = np.uint64(mt)
+        out[0, :, t] = (Cc[:, t] + m - R.mulmod(a[:, t], S[t], m)) % m
+    out[1] = a
+    return out
+
+
+def round2_terms(seed, sk, q, psi):
+    """(NTT(E) [2][dnum][T][N], S [T][N], mods): round2(seed, joint, ...) = joint S + NTT(E)."""
+    N, L, dn, al, T = _dims(sk, q)
+    S, mods, roots = R.s_ext(sk, q, psi)
+    E = round2_errors(seed, N, dn)
+    En = np.stack([np.stack([_ntt_small(E[v, j], mods, roots) for j in range(dn)]) for v in range(2)])
+    return En, S, mods
+
+
+def round2_from_terms(terms, joint):
+    """round2(seed, joint, sk, q, psi) from round2_terms(seed, sk, q, psi)."""
+    En, S, mods = terms
+    joint = np.asarray(joint, np.uint64)
+    out = np.empty_like(joint)
+    for t, mt in enumerate(mods):
+        m = np.uint64(mt)
+        out[:, :, t] = (R.mulmod(joint[:, :, t], S[t], m) + En[:, :, t]) % m
+    return out
+
+
+def first_index_with_galois_above(N, bound):
+    """The smallest r > 0 with 5^r mod 2N > bound."""
+    r, g = 1, 5 % (2 * N)
+    while g <= bound:
+        r, g = r + 1, (g * 5) % (2 * N)
+    return r

@@ -2,8 +2,10 @@
 reproduces the oracle's EvalMult key draw; the keys its protocol makes hide one small integer
 polynomial per digit, the same in every tower of Q u P and below the worst-case bound; and the
 oracle's EvalMult / ModReduce and the rotation reference under those keys decode under sum s_i to
-x^2, its roll and its windowed sum.  And, with no device: the library exports the three entry points
-and they refuse a NULL context."""
+x^2, its roll and its windowed sum.  The helpers of tests/test_gpu_multikey_edges.py (planted keys, the
+share and round-2 references with their NTTs done once, chain_step, the first index whose Galois element
+passes a bound) are held to the same parts, and a sparse batch rotates under joint keys.  And, with no
+device: the library exports the three entry points and they refuse a NULL context."""
 import ctypes as C
 import functools
 
@@ -122,3 +124,117 @@ def test_library_exports_the_multiparty_key_calls():
     assert lib.shelfi_multi_add_eval_keys(None, arr, 1, 0, p) == _lib.SHELFI_ERR_ARG
     assert lib.shelfi_multi_mult_eval_key(None, p, p) == _lib.SHELFI_ERR_ARG
     assert lib.shelfi_abi_version() == 1
+
+
+# ---- the helpers tests/test_gpu_multikey_edges.py's sweeps lean on ----
+def _planted(x, kind, rng):
+    N, q = x["N"], x["q"]
+    mods = MK.ext_moduli(N, q)
+    dn = x["mid"].shape[1]
+    if kind == "full":
+        return MK.full_key(mods, dn, N)
+    if kind == "zero":
+        return np.zeros_like(x["mid"])
+    return MK.uniform_key(rng, mods, dn, N)
+
+
+def test_planted_keys_are_canonical_and_cover_their_range():
+    x = _setup("n11_L3_P3")
+    N, q = x["N"], x["q"]
+    mods = MK.ext_moduli(N, q)
+    _, m2, _ = R.s_ext(x["sks"][0], q, x["psi"])
+    assert [int(v) for v in mods] == [int(v) for v in m2] and len(mods) == x["mid"].shape[2]
+    u = MK.uniform_key(np.random.default_rng(1), mods, 2, N)
+    f = MK.full_key(mods, 2, N)
+    assert u.shape == f.shape == x["mid"].shape and u.dtype == f.dtype == np.uint64
+    assert (u < mods[None, None, :, None]).all() and (f + np.uint64(1) == mods[None, None, :, None]).all()
+    # uniform: the top bit of every tower's range is drawn, and no two rows agree
+    assert ((u.max(axis=-1) >> np.uint64(1)) >= (mods >> np.uint64(2))[None, None]).all()
+    assert len({r.tobytes() for r in u.reshape(-1, N)}) == u.size // N
+
+
+@pytest.mark.parametrize("cid", ["n11_L3_P3", "n12_L4_30bit_P3"])
+@pytest.mark.parametrize("kind", ["full", "zero", "uniform"])
+def test_share_from_terms_is_share(cid, kind):
+    """share_terms / share_from_terms restate share(..., prev) for any prev, at the EvalMult index and at
+    both ends of the rotation range; the share hides the same small error whatever prev holds."""
+    x = _setup(cid)
+    N, q, psi, sd, sk = x["N"], x["q"], x["psi"], x["seeds"][1], x["sks"][1]
+    prev = _planted(x, kind, np.random.default_rng(3))
+    for r in (0, 1, -(N // 2 - 1)):
+        terms = MK.share_terms(sd, sk, q, psi, r)
+        got = MK.share_from_terms(terms, prev)
+        assert np.array_equal(got, MK.share(sd, sk, q, psi, r, prev))
+        other = prev.copy()
+        other[0] = 0  # prev's b-vector is not read
+        assert np.array_equal(MK.share_from_terms(terms, other), got)
+        e = MK.switch_key_error(got, r, sk, q, psi)
+        assert (e == e[:, :1]).all() and 0 < np.abs(e).max() < MK.B_ERR
+        assert np.array_equal(e, MK.switch_key_error(MK.share(sd, sk, q, psi, r), r, sk, q, psi))
+
+
+@pytest.mark.parametrize("cid", ["n11_L3_P3", "n12_L4_30bit_P3"])
+@pytest.mark.parametrize("kind", ["full", "zero", "uniform"])
+def test_round2_from_terms_is_round2(cid, kind):
+    x = _setup(cid)
+    q, psi, sd, sk = x["q"], x["psi"], x["seeds"][2], x["sks"][2]
+    joint = _planted(x, kind, np.random.default_rng(4))
+    terms = MK.round2_terms(sd, sk, q, psi)
+    got = MK.round2_from_terms(terms, joint)
+    assert np.array_equal(got, MK.round2(sd, joint, sk, q, psi))
+    if kind == "zero":
+        assert np.array_equal(got, terms[0])
+
+
+@pytest.mark.parametrize("cid", ["n11_L3_P3", "n12_L4_30bit_P3"])
+def test_chain_step_is_a_key_chain(cid):
+    """chain_step over the oracle's own lead key: the secret is the oracle's for that seed, a is kept, and
+    b + a (s_0 + s_1) is e_0 + e_1 -- small, the same in every tower; over any prev, b - prev.b + a s_1 is
+    the seed's e_1."""
+    x = _setup(cid)
+    N, q, psi = x["N"], x["q"], x["psi"]
+    s0, e0, a0 = O.sample_keygen(41, N, q)
+    sk0, pk0 = O.keygen(s0, e0, a0, q, psi)
+    s1, e1, a1 = O.sample_keygen(42, N, q)
+    pk1, sk1 = MK.chain_step(42, pk0, q, psi)
+    assert np.array_equal(sk1, O.keygen(s1, e1, a1, q, psi)[0]) and np.array_equal(pk1[1], pk0[1])
+    both = MK.sk_sum([sk0, sk1], q)
+    mods = MK.ext_moduli(N, q)[:len(q)]
+    for t in range(len(q)):
+        m = np.uint64(q[t])
+        d = (pk1[0, t] + R.mulmod(pk1[1, t], both[t], m)) % m
+        assert np.array_equal(O.to_signed(O.ntt_inv(d, q[t], psi[t]), q[t]), e0 + e1)
+    rng = np.random.default_rng(6)
+    prevs = [np.stack([rng.integers(0, int(m), size=(2, N), dtype=np.uint64) for m in mods], axis=1),
+             np.zeros((2, len(q), N), np.uint64), np.broadcast_to((mods - np.uint64(1))[None, :, None],
+                                                                  (2, len(q), N)).copy()]
+    for prev in prevs:
+        pk, sk = MK.chain_step(42, prev, q, psi)
+        assert np.array_equal(sk, sk1) and np.array_equal(pk[1], prev[1])
+        for t in range(len(q)):
+            m = np.uint64(q[t])
+            d = (pk[0, t] + (m - prev[0, t]) % m + R.mulmod(prev[1, t], sk[t], m)) % m
+            assert np.array_equal(O.to_signed(O.ntt_inv(d, q[t], psi[t]), q[t]), e1)
+
+
+def test_first_index_with_galois_above():
+    N = 1 << 17
+    r = MK.first_index_with_galois_above(N, 1 << 17)
+    assert r > 0 and R.galois(N, r) > 1 << 17
+    assert all(R.galois(N, k) <= 1 << 17 for k in range(1, r))
+    assert MK.first_index_with_galois_above(2048, 4) == 1 and MK.first_index_with_galois_above(2048, 5) == 2
+
+
+def test_sparse_rotation_under_joint_keys():
+    """A batch below N / 2 (sparse packing): the joint rotation keys of indices 1 and batch - 1 rotate the
+    batch's slots, decrypted under sum s_i."""
+    x = _setup("n11_L3_P3")
+    N, q, psi, sk = x["N"], x["q"], x["psi"], x["sk"]
+    S, d = N // 8, float(q[-1])
+    _, rot, _ = MK.protocol(x["seeds"], x["sks"], q, psi, indices=(S - 1,))
+    rot[1] = x["rot"][1]
+    v = np.random.default_rng(9).uniform(-1, 1, S)
+    ct = O.encrypt_vector(v, x["pk"], q, psi, N, S, d, seed=8)
+    for r in (1, S - 1):
+        dec = O.decrypt_vector(R.rotate_ref(ct, r, rot[r], q, psi), sk, q, psi, S, d, S)
+        assert np.abs(dec - np.roll(v, -r)).max() < 1e-6, r
