@@ -195,6 +195,18 @@ SIGNATURES = {
     "shelfi_eval_chunk_count": (C.c_uint64, [C.c_void_p]),
     "shelfi_dev_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                  C.c_void_p]),
+    # plaintext operands, EvalSub, EvalNegate (dev_api.cpp, plain.hip)
+    "shelfi_dev_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_double, C.c_void_p,
+                                    C.c_void_p]),
+    "shelfi_dev_mult_plain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
+                                        C.c_void_p, C.c_void_p]),
+    "shelfi_dev_add_plain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
+                                       C.c_void_p, C.c_void_p]),
+    "shelfi_dev_sub_plain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
+                                       C.c_void_p, C.c_void_p]),
+    "shelfi_dev_sub": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                 C.c_void_p]),
+    "shelfi_dev_negate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     # threshold CKKS (mkhe.cpp RunCKKS): key chain, partial decryption, fusion (threshold.hip)
     "shelfi_multiparty_keygen": (C.c_int, [C.c_void_p, u64p]),
     "shelfi_set_threshold_noise": (C.c_int, [C.c_void_p, C.c_double]),

@@ -547,6 +547,90 @@ def add(ckks, a, b, out=None):
     return out
 
 
+def sub(ckks, a, b, out=None):
+    """cc->EvalSub(a, b) for K ciphertext pairs of the same level and scale: out = a - b mod q_t
+    (out may be a or b).  Needs no keys; enqueued on a's stream."""
+    _check_ct(a, ckks, any_level=True)
+    _check_ct(b, ckks, a.shape[0], any_level=True)
+    if a.shape != b.shape or b.device != a.device:
+        raise ValueError("EvalSub operands must have the same shape (same level) and device")
+    out = _like(ckks, a, out)
+    check(_lib.load().shelfi_dev_sub(ckks._ctx, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), a.shape[0],
+                                     int(a.shape[2]), C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(a))),
+          "dev_sub")
+    return out
+
+
+def neg(ckks, ct, out=None):
+    """cc->EvalNegate(ct): out = -ct mod q_t (out may be ct).  Needs no keys; enqueued on ct's stream."""
+    _check_ct(ct, ckks, any_level=True)
+    out = _like(ckks, ct, out)
+    check(_lib.load().shelfi_dev_negate(ckks._ctx, C.c_void_p(ct.data_ptr()), ct.shape[0], int(ct.shape[2]),
+                                        C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(ct))), "dev_negate")
+    return out
+
+
+def encode(ckks, x, towers=None, scale=None, out=None):
+    """cc->MakeCKKSPackedPlaintext without the Encrypt: a float64 CUDA vector of n values -> K =
+    ceil(n / batch) plaintexts, an int64 tensor [K][towers][N] (EVALUATION, canonical residues), by the
+    encode inside encrypt exactly.  towers defaults to L and scale to the context's delta (an operand
+    for add_plain / sub_plain on a fresh ciphertext); a factor for mult_plain whose product is to be
+    rescale()d back to the ciphertext's scale is encoded at scale=float(q[towers - 1]).  A coefficient
+    above 2^61 in magnitude, or a non-finite value, raises ValueError.  Needs no keys."""
+    torch = _torch()
+    if not x.is_cuda or x.dtype != torch.float64 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous float64 CUDA tensor")
+    inf = ckks.info()
+    L, N, B = inf["num_towers"], inf["ring_dim"], inf["batch"]
+    towers = L if towers is None else int(towers)
+    scale = float(inf["delta"] if scale is None else scale)
+    if not 0 <= towers < 1 << 32:
+        raise ValueError("tower count out of range for this context")
+    K = (x.numel() + B - 1) // B
+    if out is None:
+        out = torch.empty((K, max(towers, 0), N), dtype=torch.int64, device=x.device)
+    if (not out.is_cuda or not out.is_contiguous() or out.element_size() != 8 or tuple(out.shape) != (K, towers, N)
+            or out.device != x.device):
+        raise ValueError("out must be a contiguous [K][towers][N] 64-bit tensor on x's device")
+    check(_lib.load().shelfi_dev_encode(ckks._ctx, C.c_void_p(x.data_ptr()), x.numel(), towers, scale,
+                                        C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(x))), "dev_encode")
+    return out
+
+
+def _plain_op(fn, what, ckks, ct, pt, out):
+    _check_ct(ct, ckks, any_level=True)
+    K, _, l, N = ct.shape
+    if not pt.is_cuda or not pt.is_contiguous() or pt.element_size() != 8 or pt.device != ct.device:
+        raise ValueError("plaintext tensors must be contiguous 64-bit CUDA tensors on the ciphertexts' device")
+    sh = tuple(pt.shape)
+    if len(sh) == 2:  # one plaintext [towers][N] for every ciphertext
+        sh = (1,) + sh
+    if len(sh) != 3 or sh[1:] != (l, N) or sh[0] not in (1, K):
+        raise ValueError("plaintext tensor must have shape [K][towers][N] = [%d][%d][%d], or hold one plaintext"
+                         % (K, l, N))
+    out = _like(ckks, ct, out)
+    check(fn(ckks._ctx, C.c_void_p(ct.data_ptr()), C.c_void_p(pt.data_ptr()), K, sh[0], int(l),
+             C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(ct))), what)
+    return out
+
+
+def mult_plain(ckks, ct, pt, out=None):
+    """cc->EvalMult(ct, pt): both components of K ciphertexts [K][2][l][N] times the plaintexts pt
+    [K][l][N] (or one plaintext, [1][l][N] or [l][N], for every ciphertext); out may be ct.  Scale:
+    scale_ct * scale_pt.  Needs no keys; enqueued on ct's stream."""
+    return _plain_op(_lib.load().shelfi_dev_mult_plain, "dev_mult_plain", ckks, ct, pt, out)
+
+
+def add_plain(ckks, ct, pt, out=None):
+    """cc->EvalAdd(ct, pt): c0 + pt, c1 unchanged; pt as for mult_plain, at the ciphertext's scale."""
+    return _plain_op(_lib.load().shelfi_dev_add_plain, "dev_add_plain", ckks, ct, pt, out)
+
+
+def sub_plain(ckks, ct, pt, out=None):
+    """cc->EvalSub(ct, pt): c0 - pt, c1 unchanged; pt as for mult_plain, at the ciphertext's scale."""
+    return _plain_op(_lib.load().shelfi_dev_sub_plain, "dev_sub_plain", ckks, ct, pt, out)
+
+
 def ntt(ckks, polys, inverse: bool = False):
     """In-place negacyclic NTT (PALISADE order) of [P][N] polys; tower = p % L."""
     inf = ckks.info()

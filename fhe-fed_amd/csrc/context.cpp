@@ -205,6 +205,7 @@ void build_ntt_tables(const Params& p, DeviceTables& dt) {
       c.red_r = c.red_ok ? (uint32_t)(((u128)1 << (32 + E)) / q) : 0;
       c.crt_sh = E >= 31 ? E - 31 : 0;
       c.bq62 = ((1ull << 62) / q) * q;
+      c.bmu = E <= 59 ? (uint64_t)(((u128)1 << (2 * E + 2)) / q) : 0;  // plain_mulmod takes q < 2^60
       c.inv_q32 = (float)((double)(1ull << c.crt_sh) / (double)q);
     }
     // twiddles: psi^bitrev(i), psi^-bitrev(i)

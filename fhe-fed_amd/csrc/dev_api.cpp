@@ -1,5 +1,6 @@
 // dev_api.cpp — the device API (shelfi_dev_*: device buffers in, device buffers out, the caller's
 // stream) and the packed resident arena it aggregates from.
+#include <cmath>
 #include <cstring>
 #include <mutex>
 
@@ -542,6 +543,97 @@ int shelfi_dev_encrypt(shelfi_ctx* ctx, const double* x_dev, size_t n, uint64_t*
 int shelfi_dev_decrypt(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, double scale, size_t n,
                        double* out_dev, void* stream) {
   return dev_decrypt(ctx, ct_dev, K, ctx ? ctx->p.L : 0, scale, n, out_dev, stream);
+}
+
+// ---- plaintext operands (plain.hip) ----
+int shelfi_dev_encode(shelfi_ctx* ctx, const double* x_dev, size_t n, uint32_t towers, double scale,
+                      uint64_t* pt_dev, void* stream) {
+  if (!ctx || (n && (!x_dev || !pt_dev))) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    const Params& p = ctx->p;
+    if (towers < 1 || towers > p.L) throw Error{SHELFI_ERR_ARG, "tower count out of range for this context"};
+    if (!(scale > 0.0) || !std::isfinite(scale)) throw Error{SHELFI_ERR_ARG, "encode: the scale must be finite and positive"};
+    const uint64_t K = (n + p.batch - 1) / p.batch;
+    if (!K) return;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t kc_max = dev_chunk(K, encode_scratch_bytes(p, 1));
+    void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, encode_scratch_bytes(p, kc_max));
+    const GenFlag fl = next_gen_flag(ctx);  // the call's own generation of the range words
+    const size_t pt_words = (size_t)towers * p.N;
+    for (uint64_t k0 = 0; k0 < K; k0 += kc_max) {
+      const uint64_t kc = std::min(kc_max, K - k0);
+      const uint64_t xs = k0 * p.batch, xn = std::min<uint64_t>(n - xs, kc * p.batch);
+      launch_encode_plain(p, ctx->dt, x_dev + xs, xn, kc, towers, scale, pt_dev + k0 * pt_words, scratch, fl, s);
+    }
+    SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call; the range words are final
+    if (gen_flag_raised(ctx, fl, 1)) throw Error{SHELFI_ERR_RANGE, "encode: non-finite input value"};
+    if (gen_flag_raised(ctx, fl, 0))
+      throw Error{SHELFI_ERR_RANGE, "encode: a coefficient |x * scale| above 2^61 (the plaintext encode has no large-value path)"};
+  });
+}
+
+namespace {
+bool words_overlap(const uint64_t* a, const uint64_t* b, uint64_t na, uint64_t nb) { return a < b + nb && b < a + na; }
+
+// the three ciphertext-with-plaintext calls: op as launch_plain_op takes it
+int dev_plain_op(int op, shelfi_ctx* ctx, const uint64_t* ct_dev, const uint64_t* pt_dev, size_t K, size_t Kp,
+                 uint32_t towers, uint64_t* out_dev, void* stream) {
+  if (!ctx || (K && (!ct_dev || !pt_dev || !out_dev))) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    const Params& p = ctx->p;
+    if (towers < 1 || towers > p.L) throw Error{SHELFI_ERR_ARG, "tower count out of range for this context"};
+    if (!K) return;
+    if (Kp != 1 && Kp != K) throw Error{SHELFI_ERR_ARG, "plaintext operand: one plaintext per ciphertext, or one for all"};
+    // each thread reads its residues before writing them: out may be ct exactly, not shifted
+    const uint64_t cw = 2ull * towers * p.N * K, pw = (uint64_t)towers * p.N * Kp;
+    if ((out_dev != ct_dev && words_overlap(ct_dev, out_dev, cw, cw)) || words_overlap(pt_dev, out_dev, pw, cw))
+      throw Error{SHELFI_ERR_ARG, "plaintext operand: the output must be the ciphertext input exactly or overlap no input"};
+    DeviceGuard g(ctx->device);
+    launch_plain_op(op, ct_dev, pt_dev, K, Kp, towers, p.logN, ctx->dt.tc, out_dev, (hipStream_t)stream);
+  });
+}
+
+// EvalSub (b_dev set) and EvalNegate (b_dev null)
+int dev_ct_sub(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev, bool neg, size_t K, uint32_t towers,
+               uint64_t* out_dev, void* stream) {
+  if (!ctx || (K && (!a_dev || (!neg && !b_dev) || !out_dev))) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    const Params& p = ctx->p;
+    if (towers < 1 || towers > p.L) throw Error{SHELFI_ERR_ARG, "tower count out of range for this context"};
+    if (!K) return;
+    const uint64_t words = 2ull * towers * p.N * K;
+    for (const uint64_t* in : {a_dev, b_dev})
+      if (in && out_dev != in && words_overlap(in, out_dev, words, words))
+        throw Error{SHELFI_ERR_ARG, "EvalSub / EvalNegate output must be an input exactly or not overlap the inputs"};
+    DeviceGuard g(ctx->device);
+    launch_ct_sub(a_dev, neg ? nullptr : b_dev, K * 2 * towers, towers, p.logN, ctx->dt.tc, out_dev, (hipStream_t)stream);
+  });
+}
+}  // namespace
+
+int shelfi_dev_mult_plain(shelfi_ctx* ctx, const uint64_t* ct_dev, const uint64_t* pt_dev, size_t K, size_t Kp,
+                          uint32_t towers, uint64_t* out_dev, void* stream) {
+  return dev_plain_op(0, ctx, ct_dev, pt_dev, K, Kp, towers, out_dev, stream);
+}
+int shelfi_dev_add_plain(shelfi_ctx* ctx, const uint64_t* ct_dev, const uint64_t* pt_dev, size_t K, size_t Kp,
+                         uint32_t towers, uint64_t* out_dev, void* stream) {
+  return dev_plain_op(1, ctx, ct_dev, pt_dev, K, Kp, towers, out_dev, stream);
+}
+int shelfi_dev_sub_plain(shelfi_ctx* ctx, const uint64_t* ct_dev, const uint64_t* pt_dev, size_t K, size_t Kp,
+                         uint32_t towers, uint64_t* out_dev, void* stream) {
+  return dev_plain_op(2, ctx, ct_dev, pt_dev, K, Kp, towers, out_dev, stream);
+}
+int shelfi_dev_sub(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev, size_t K, uint32_t towers,
+                   uint64_t* out_dev, void* stream) {
+  return dev_ct_sub(ctx, a_dev, b_dev, false, K, towers, out_dev, stream);
+}
+int shelfi_dev_negate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, uint64_t* out_dev,
+                      void* stream) {
+  return dev_ct_sub(ctx, ct_dev, nullptr, true, K, towers, out_dev, stream);
 }
 
 int shelfi_dev_decrypt_level(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, double scale,

@@ -962,8 +962,8 @@ size_t encrypt_scratch_bytes(const Params& p, uint64_t K) {
 }
 
 // encode's FFTSpecialInv of K slot vectors (x: n doubles, zero-padded) into fbuf [K][S] (complex)
-static void launch_encode_fft(const Params& p, const DeviceTables& dt, const double* x, uint64_t n, uint64_t K,
-                              double2* fbuf, hipStream_t s) {
+void launch_encode_fft(const Params& p, const DeviceTables& dt, const double* x, uint64_t n, uint64_t K,
+                       double2* fbuf, hipStream_t s) {
   const uint32_t logS = __builtin_ctz(p.batch);
   const uint32_t blkLog = fft_block_log(logS);
   const int logR = (int)(logS - blkLog);

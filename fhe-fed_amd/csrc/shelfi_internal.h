@@ -145,6 +145,9 @@ struct TowerConst {
   // |X'| >= crt_edge = (Q - 1) / 2 - floor(Q 2^-16) as {low, high} 64-bit words (the same in every
   // tower; all ones when that is 2^127 or more: the 128-bit range test then covers it)
   uint64_t crt_edge[2];
+  // Barrett's constant for a product of two canonical residues (plain.hip plain_mulmod):
+  // floor(2^(2 E + 2) / q), E = bitlength(q) - 1
+  uint64_t bmu;
 };
 
 constexpr int kEncVTab = 4 * 81, kEncETab = 128, kEncTab = kEncVTab + kEncETab;
@@ -406,6 +409,23 @@ void launch_encrypt_approx(const Params& p, const DeviceTables& dt, const Device
                            uint64_t n, uint64_t K, uint64_t* ct, void* scratch, const uint32_t key[8],
                            uint64_t g0, hipStream_t s);
 size_t encrypt_scratch_bytes(const Params& p, uint64_t K);
+// encode's FFTSpecialInv of K slot vectors (x: n doubles, zero-padded) into fbuf [K][S] (encrypt.hip)
+void launch_encode_fft(const Params& p, const DeviceTables& dt, const double* x, uint64_t n, uint64_t K,
+                       double2* fbuf, hipStream_t s);
+// ---- plaintext operands (plain.hip) ----
+// cc->MakeCKKSPackedPlaintext without the Encrypt: n doubles -> K plaintexts pt [K][towers][N] at `scale`,
+// EVALUATION, canonical; scratch = encode_scratch_bytes(p, K).  GenFlag word 0: a finite |m| above 2^61,
+// word 1: a non-finite value (the residues are then meaningless; the caller refuses the call).
+size_t encode_scratch_bytes(const Params& p, uint64_t K);
+void launch_encode_plain(const Params& p, const DeviceTables& dt, const double* x, uint64_t n, uint64_t K,
+                         uint32_t towers, double scale, uint64_t* pt, void* scratch, GenFlag flag, hipStream_t s);
+// op 0 / 1 / 2: out = ct * pt (both components) / (c0 + pt, c1) / (c0 - pt, c1); ct, out [K][2][towers][N]
+// (out may be ct), pt [Kp][towers][N] with Kp = K or 1
+void launch_plain_op(int op, const uint64_t* ct, const uint64_t* pt, uint64_t K, uint64_t Kp, uint32_t towers,
+                     uint32_t logN, const TowerConst* tq, uint64_t* out, hipStream_t s);
+// out = a - b mod q_t, or -a when b is null, over rows = K * 2 * Ll polynomials (out may be an input)
+void launch_ct_sub(const uint64_t* a, const uint64_t* b, uint64_t rows, uint32_t Ll, uint32_t logN,
+                   const TowerConst* tq, uint64_t* out, hipStream_t s);
 // Decode noise flooding (PALISADE 1.11 Decode); off = exact decode.
 struct DecodeNoise {
   int enabled = 0;

@@ -452,6 +452,44 @@ uint64_t shelfi_eval_chunk_count(const shelfi_ctx* ctx);
 int shelfi_dev_add(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev, size_t K, uint32_t towers,
                    uint64_t* out_dev, void* stream);
 
+/* ---- plaintext operands, EvalSub, EvalNegate (PALISADE's SHE calls) ---------- *
+ * A plaintext batch is uint64 [Kp][towers][N] in HBM: EVALUATION form, canonical residues < q_t, tower t
+ * over q_t of the context's chain, towers in 1..L as for shelfi_dev_decrypt_level.  The API carries no
+ * metadata: the caller tracks scales.  None of the six calls needs a key.  towers of 0 or above L, and a
+ * NULL buffer with work to do, are SHELFI_ERR_ARG. */
+/* cc->MakeCKKSPackedPlaintext (ckks.cpp:80, mkhe.cpp:145) without the Encrypt: n doubles become
+ * K = ceil(n / batch) plaintexts, zero-padded like shelfi_dev_encrypt, by the encode inside encrypt
+ * exactly: FFTSpecialInv, m_j = round_half_away(fl(fl(v / S) * scale)), reduced into the first `towers`
+ * towers, forward NTT.  `scale` is any finite positive double (else SHELFI_ERR_ARG): pass the context's
+ * delta for an operand of a fresh ciphertext's scale (add / sub), and (double)q_{towers-1} for a factor
+ * whose product is to be rescaled (shelfi_dev_rescale) back to the ciphertext's own scale.
+ * |m_j| <= 2^61 is the whole supported range: a larger finite coefficient is SHELFI_ERR_RANGE (PALISADE's
+ * approxFactor scale-down, encrypt's large-value path, is not restated for plaintexts), a non-finite one
+ * is refused as encrypt refuses it; pt_dev is then unspecified.  Uses the context's scratch in chunks of
+ * SHELFI_DEV_CHUNK_MIB (16 * batch + 64 bytes per plaintext) and synchronises `stream` before returning. */
+int shelfi_dev_encode(shelfi_ctx* ctx, const double* x_dev, size_t n, uint32_t towers, double scale,
+                      uint64_t* pt_dev, void* stream);
+/* cc->EvalMult(ct, pt): both components times the plaintext; ct_dev, out_dev [K][2][towers][N], pt_dev
+ * [Kp][towers][N] with Kp = K, or Kp = 1 (one plaintext for every ciphertext); any other Kp is
+ * SHELFI_ERR_ARG.  Scale: scale_ct * scale_pt.  This and the four calls below need no scratch and
+ * return with the work enqueued on `stream`; K = 0 is a no-op; every output residue is canonical; out
+ * may be the ciphertext input exactly (either one for shelfi_dev_sub), and must overlap no input
+ * otherwise. */
+int shelfi_dev_mult_plain(shelfi_ctx* ctx, const uint64_t* ct_dev, const uint64_t* pt_dev, size_t K, size_t Kp,
+                          uint32_t towers, uint64_t* out_dev, void* stream);
+/* cc->EvalAdd(ct, pt) / cc->EvalSub(ct, pt): c0 +- pt, c1 copied (nothing to copy when out == ct); the
+ * plaintext's scale must be the ciphertext's.  Kp as above. */
+int shelfi_dev_add_plain(shelfi_ctx* ctx, const uint64_t* ct_dev, const uint64_t* pt_dev, size_t K, size_t Kp,
+                         uint32_t towers, uint64_t* out_dev, void* stream);
+int shelfi_dev_sub_plain(shelfi_ctx* ctx, const uint64_t* ct_dev, const uint64_t* pt_dev, size_t K, size_t Kp,
+                         uint32_t towers, uint64_t* out_dev, void* stream);
+/* cc->EvalSub(ct_a, ct_b): out = a - b mod q_t over [K][2][towers][N] (same level and scale). */
+int shelfi_dev_sub(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev, size_t K, uint32_t towers,
+                   uint64_t* out_dev, void* stream);
+/* cc->EvalNegate(ct): out = -ct mod q_t. */
+int shelfi_dev_negate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, uint64_t* out_dev,
+                      void* stream);
+
 /* ---- threshold CKKS (the reference's code/mkhe/mkhe.cpp RunCKKS, lines 188-465) ---- *
  * P parties hold additive shares s_i of one secret key; a ciphertext under the joint public key
  * decrypts only when every party contributes a partial decryption.  Encrypt and
