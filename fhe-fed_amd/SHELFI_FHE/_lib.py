@@ -159,7 +159,7 @@ SIGNATURES = {
     "shelfi_dev_decrypt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_size_t,
                                      C.c_void_p, C.c_void_p]),
     "shelfi_dev_ntt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
-    # EvalMult / relinearization / ModReduce (eval.cpp, keyswitch.hip)
+    # EvalMult / relinearization / ModReduce (eval_keys.cpp, dev_api.cpp, keyswitch.hip)
     "shelfi_special_primes": (C.c_int, [C.c_uint32, C.c_uint32, u64p, C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64p, u64p]),
     "shelfi_eval_key_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
@@ -180,7 +180,7 @@ SIGNATURES = {
     "shelfi_palisade_evalkey_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, u64p]),
     "shelfi_palisade_evalkey_rewrite": (C.c_int, [C.c_char_p, C.c_size_t, u64p, C.POINTER(u8p),
                                                   C.POINTER(C.c_size_t)]),
-    # slot rotations and EvalSum (mkhe.cpp:124, :274, :372; eval.cpp, rotate.hip)
+    # slot rotations and EvalSum (mkhe.cpp:124, :274, :372; eval_keys.cpp, dev_api.cpp, rotate.hip)
     "shelfi_galois_element": (C.c_int, [C.c_uint32, C.c_int32, C.POINTER(C.c_uint32)]),
     "shelfi_rotation_keygen": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t]),
     "shelfi_eval_sum_keygen": (C.c_int, [C.c_void_p]),
@@ -223,7 +223,7 @@ SIGNATURES = {
     "shelfi_partial_blob_pack": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_double,
                                            C.c_uint64, C.c_uint64, C.c_int, u64p, C.POINTER(u8p),
                                            C.POINTER(C.c_size_t)]),
-    # multiparty evaluation keys (mkhe.cpp:271-317; eval.cpp, multikey.hip)
+    # multiparty evaluation keys (mkhe.cpp:271-317; eval_keys.cpp, multikey.hip)
     "shelfi_multi_key_switch_gen": (C.c_int, [C.c_void_p, C.c_int32, u64p, u64p]),
     "shelfi_multi_add_eval_keys": (C.c_int, [C.c_void_p, C.POINTER(u64p), C.c_size_t, C.c_int, u64p]),
     "shelfi_multi_mult_eval_key": (C.c_int, [C.c_void_p, u64p, u64p]),

@@ -1,12 +1,16 @@
 // api_internal.h — declarations shared by the C-ABI sources only (context.cpp, wire.cpp, call_state.cpp,
-// bytes_api.cpp, dev_api.cpp).  The contract with the kernels, eval.cpp and comm.cpp is shelfi_internal.h.
+// bytes_api.cpp, dev_api.cpp, dev_arena.cpp, eval_state.cpp, eval_keys.cpp).  The contract with the kernels
+// and comm.cpp is shelfi_internal.h; the evaluation state's own declarations are in eval_internal.h.
 #pragma once
 
 #include <string.h>
 
+#include <algorithm>
 #include <cstdint>
+#include <initializer_list>
 #include <vector>
 
+#include "api_util.h"
 #include "host_stage.h"
 #include "shelfi_internal.h"
 
@@ -15,8 +19,48 @@
 
 namespace shelfi {
 
+// ------------------------------------------------------- chunked calls ----
+// Ciphertexts per launch chain of a device call: K split evenly over the fewest chains whose scratch
+// (per_ct bytes a ciphertext) fits a budget of budget_mib MiB, so no launch runs a short tail chunk.
+inline uint64_t chunk_split(uint64_t K, uint64_t budget_mib, size_t per_ct) {
+  const uint64_t cap = std::max<uint64_t>(1, (budget_mib << 20) / std::max<size_t>(per_ct, 1));
+  const uint64_t n = (K + cap - 1) / cap;
+  return n ? (K + n - 1) / n : 1;
+}
+
+// The chunk loop of a device call over K ciphertexts, a chain of kc needing scratch_bytes_of(kc) bytes: the
+// context's scratch grown once for the largest chain, then body(k0, kc, scratch) for ciphertexts [k0, k0 + kc)
+// of every chain in turn.  Returns the number of chains; they share the scratch, so the caller synchronises
+// its stream before the next call.  budget_mib: switches().dev_chunk_mib or switches().eval_chunk_mib.
+template <class ScratchBytesOf, class Body>
+uint64_t for_chunks(shelfi_ctx* ctx, uint64_t K, uint64_t budget_mib, ScratchBytesOf scratch_bytes_of, Body body) {
+  const uint64_t kc_max = chunk_split(K, budget_mib, scratch_bytes_of(1));
+  void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, scratch_bytes_of(kc_max));
+  uint64_t chains = 0;
+  for (uint64_t k0 = 0; k0 < K; k0 += kc_max, ++chains) body(k0, std::min(kc_max, K - k0), scratch);
+  return chains;
+}
+
+// ------------------------------------------------------ operand checks ----
+// do the word ranges [a, a + na) and [b, b + nb) share a word?
+inline bool words_overlap(const uint64_t* a, uint64_t na, const uint64_t* b, uint64_t nb) {
+  return a < b + nb && b < a + na;
+}
+// A pointwise call reads each residue before it writes it: its output may be one of its inputs exactly, but
+// must not overlap an input at a shift (out and every input `words` words long; a null input is absent).
+inline bool out_exact_or_apart(const uint64_t* out, uint64_t words, std::initializer_list<const uint64_t*> ins) {
+  for (const uint64_t* in : ins)
+    if (in && in != out && words_overlap(in, words, out, words)) return false;
+  return true;
+}
+inline void require_towers(const Params& p, uint32_t towers) {
+  if (towers < 1 || towers > p.L) throw Error{SHELFI_ERR_ARG, "tower count out of range for this context"};
+}
+
 // ---------------------------------------------------------- context.cpp ----
-// encryption/keygen stream key + first ciphertext index for this call
+// the ChaCha20 key of a call that draws randomness: the context's seed, or OS entropy per call
+void stream_key(const shelfi_ctx* ctx, uint32_t key[8]);
+// encryption stream key + first ciphertext index for this call
 void draw_key(shelfi_ctx* ctx, uint64_t count, uint32_t key[8], uint64_t* g0);
 
 // Zeroes a call's stream key when the call leaves its scope, by return or by exception.

@@ -1,5 +1,5 @@
 // api_util.h — host helpers shared by the C-ABI sources (context.cpp, wire.cpp, call_state.cpp,
-// bytes_api.cpp, dev_api.cpp, eval.cpp).
+// bytes_api.cpp, dev_api.cpp, dev_arena.cpp, eval_state.cpp, eval_keys.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -45,26 +45,30 @@ inline int guarded(F&& f) {
   }
 }
 
-inline void dfree(void*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
 template <class T>
 inline void dfree_t(T*& p) {
-  void* v = p;
-  dfree(v);
+  if (p) (void)hipFree(p);
   p = nullptr;
 }
 
 inline void* ensure(void*& buf, size_t& cap, size_t bytes) {
   if (bytes <= cap && buf) return buf;
-  dfree(buf);
+  dfree_t(buf);
   cap = 0;
   size_t want = bytes < 64 ? 64 : bytes;
   SHELFI_HIP(hipMalloc(&buf, want));
   cap = want;
   return buf;
 }
+
+// A call's own device buffer of `words` uint64 words, freed when the call leaves its scope.
+struct DevWords {
+  uint64_t* p = nullptr;
+  explicit DevWords(size_t words) { SHELFI_HIP(hipMalloc((void**)&p, (words ? words : 1) * 8)); }
+  ~DevWords() { (void)hipFree(p); }
+  DevWords(const DevWords&) = delete;
+  DevWords& operator=(const DevWords&) = delete;
+};
 
 template <class T>
 inline T* upload(const T* host, size_t count) {

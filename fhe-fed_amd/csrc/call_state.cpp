@@ -7,6 +7,7 @@
 
 #include "api_internal.h"
 #include "api_util.h"
+#include "eval_internal.h"
 
 using namespace shelfi;
 
@@ -117,7 +118,7 @@ static uint32_t decode_towers(const Params& p, uint32_t towers) {
 DecodePass decode_pass(shelfi_ctx* ctx, uint32_t towers, bool exact) {
   Params p = ctx->p;
   p.L = exact ? towers : decode_towers(ctx->p, towers);  // Q' = q_0 .. q_{p.L-1}; the secret key's first towers
-  return DecodePass{p, p.L == ctx->p.L ? ctx->dt : level_tables(ctx, p.L)};
+  return DecodePass{p, p.L == ctx->p.L ? ctx->dt : level_q(ctx, p.L)};
 }
 
 }  // namespace shelfi

@@ -37,7 +37,7 @@ static uint64_t compute_params_id(const Params& p) {
   return fnv1a(p.q, sizeof(uint64_t) * p.L, h);
 }
 
-void seed_to_key(uint64_t seed, uint32_t key[8]) {
+static void seed_to_key(uint64_t seed, uint32_t key[8]) {
   uint64_t st = seed;
   for (int i = 0; i < 4; ++i) {
     uint64_t z = (st += 0x9E3779B97F4A7C15ull);
@@ -49,7 +49,7 @@ void seed_to_key(uint64_t seed, uint32_t key[8]) {
   }
 }
 
-void os_random(void* buf, size_t n) {
+static void os_random(void* buf, size_t n) {
   uint8_t* p = (uint8_t*)buf;
   while (n) {
     ssize_t r = getrandom(p, n, 0);
@@ -59,16 +59,18 @@ void os_random(void* buf, size_t n) {
   }
 }
 
-// encryption/keygen stream key + first ciphertext index for this call
-void draw_key(shelfi_ctx* ctx, uint64_t count, uint32_t key[8], uint64_t* g0) {
-  if (ctx->seed) {
+void stream_key(const shelfi_ctx* ctx, uint32_t key[8]) {
+  if (ctx->seed)
     seed_to_key(ctx->seed, key);
-    *g0 = ctx->enc_counter;
-    ctx->enc_counter += count;
-  } else {
+  else
     os_random(key, 32);
-    *g0 = 0;
-  }
+}
+
+// encryption stream key + first ciphertext index for this call
+void draw_key(shelfi_ctx* ctx, uint64_t count, uint32_t key[8], uint64_t* g0) {
+  stream_key(ctx, key);
+  *g0 = ctx->seed ? ctx->enc_counter : 0;
+  if (ctx->seed) ctx->enc_counter += count;
 }
 
 // ------------------------------------------------------- tables / params ----
@@ -160,7 +162,7 @@ static uint32_t bitrev_host(uint32_t x, uint32_t bits) {
 }
 
 // NTT / CRT tables of the towers p.q[0..L) (the context's chain, one of its levels, or an
-// extended basis Q_l u P of the key switching in eval.cpp).
+// extended basis Q_l u P of the key switching in eval_state.cpp).
 void build_ntt_tables(const Params& p, DeviceTables& dt) {
   free_ntt_tables(dt);
   const uint32_t N = p.N, L = p.L;
@@ -653,8 +655,8 @@ void shelfi_ctx_destroy(shelfi_ctx* ctx) {
       if (ctx->wl_dev[i]) (void)hipFree(ctx->wl_dev[i]);
     }
     dfree_t(ctx->unit_wl);
-    dfree(ctx->scratch);
-    dfree(ctx->io);
+    dfree_t(ctx->scratch);
+    dfree_t(ctx->io);
     if (ctx->gather_host) (void)hipHostFree(ctx->gather_host);
     ctx->gather_host = nullptr;
     dfree_t(ctx->dev_flag);
@@ -726,30 +728,18 @@ int shelfi_keygen(shelfi_ctx* ctx, const char* cryptodir) {
     DeviceGuard g(ctx->device);
     const Params& p = ctx->p;
     const size_t LN = (size_t)p.L * p.N;
-    uint32_t key[8];
-    if (ctx->seed)
-      seed_to_key(ctx->seed, key);
-    else
-      os_random(key, 32);
-    void* sk_d = nullptr;
-    void* pk_d = nullptr;
-    SHELFI_HIP(hipMalloc(&sk_d, LN * 8));
-    SHELFI_HIP(hipMalloc(&pk_d, 2 * LN * 8));
-    void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, keygen_scratch_bytes(p));
     std::vector<uint64_t> sk(LN), pk(2 * LN);
-    try {
-      launch_keygen(p, ctx->dt, key, (uint64_t*)sk_d, (uint64_t*)pk_d, scratch, ctx->stream);
-      SHELFI_HIP(hipMemcpyAsync(sk.data(), sk_d, LN * 8, hipMemcpyDeviceToHost, ctx->stream));
-      SHELFI_HIP(hipMemcpyAsync(pk.data(), pk_d, 2 * LN * 8, hipMemcpyDeviceToHost, ctx->stream));
+    {
+      uint32_t key[8];
+      KeyWiper wipe(key);
+      stream_key(ctx, key);
+      DevWords sk_d(LN), pk_d(2 * LN);
+      void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, keygen_scratch_bytes(p));
+      launch_keygen(p, ctx->dt, key, sk_d.p, pk_d.p, scratch, ctx->stream);
+      SHELFI_HIP(hipMemcpyAsync(sk.data(), sk_d.p, LN * 8, hipMemcpyDeviceToHost, ctx->stream));
+      SHELFI_HIP(hipMemcpyAsync(pk.data(), pk_d.p, 2 * LN * 8, hipMemcpyDeviceToHost, ctx->stream));
       SHELFI_HIP(hipStreamSynchronize(ctx->stream));
-    } catch (...) {
-      (void)hipFree(sk_d);
-      (void)hipFree(pk_d);
-      throw;
     }
-    (void)hipFree(sk_d);
-    (void)hipFree(pk_d);
-    std::memset(key, 0, sizeof(key));
     install_keys(ctx, pk.data(), sk.data(), true);
     // ckks.cpp:36-56: context first, then public, then private key, in PALISADE 1.11's
     // cereal PortableBinary format (palisade_codec.h), so PALISADE clients can load them
@@ -777,30 +767,14 @@ int shelfi_multiparty_keygen(shelfi_ctx* ctx, const uint64_t* prev_pk) {
       if (prev_pk[i] >= p.q[(i / p.N) % p.L]) throw Error{SHELFI_ERR_FORMAT, "previous public key residue >= q"};
     uint32_t key[8];
     KeyWiper wipe(key);
-    if (ctx->seed)
-      seed_to_key(ctx->seed, key);
-    else
-      os_random(key, 32);
-    struct Bufs {
-      void* sk = nullptr;
-      void* pk = nullptr;
-      void* prev = nullptr;
-      ~Bufs() {
-        (void)hipFree(sk);
-        (void)hipFree(pk);
-        (void)hipFree(prev);
-      }
-    } d;
-    SHELFI_HIP(hipMalloc(&d.sk, LN * 8));
-    SHELFI_HIP(hipMalloc(&d.pk, 2 * LN * 8));
-    SHELFI_HIP(hipMalloc(&d.prev, 2 * LN * 8));
+    stream_key(ctx, key);
+    DevWords sk_d(LN), pk_d(2 * LN), prev_d(2 * LN);
     void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, keygen_chain_scratch_bytes(p));
     std::vector<uint64_t> sk(LN), pk(2 * LN);
-    SHELFI_HIP(hipMemcpyAsync(d.prev, prev_pk, 2 * LN * 8, hipMemcpyHostToDevice, ctx->stream));
-    launch_keygen_chain(p, ctx->dt, key, (const uint64_t*)d.prev, (uint64_t*)d.sk, (uint64_t*)d.pk, scratch,
-                        ctx->stream);
-    SHELFI_HIP(hipMemcpyAsync(sk.data(), d.sk, LN * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SHELFI_HIP(hipMemcpyAsync(pk.data(), d.pk, 2 * LN * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SHELFI_HIP(hipMemcpyAsync(prev_d.p, prev_pk, 2 * LN * 8, hipMemcpyHostToDevice, ctx->stream));
+    launch_keygen_chain(p, ctx->dt, key, prev_d.p, sk_d.p, pk_d.p, scratch, ctx->stream);
+    SHELFI_HIP(hipMemcpyAsync(sk.data(), sk_d.p, LN * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SHELFI_HIP(hipMemcpyAsync(pk.data(), pk_d.p, 2 * LN * 8, hipMemcpyDeviceToHost, ctx->stream));
     SHELFI_HIP(hipStreamSynchronize(ctx->stream));
     install_keys(ctx, pk.data(), sk.data(), false);
   });

@@ -222,7 +222,7 @@ namespace shelfi {
 class Stager;
 class AsyncDrain;
 class AsyncUpload;
-struct EvalState;  // eval.cpp: relinearization key + per-level tables
+struct EvalState;  // eval_internal.h: relinearization key + per-level tables
 }
 
 struct shelfi_ctx {
@@ -295,7 +295,7 @@ struct shelfi_ctx {
   size_t io_bytes = 0;
   uint64_t* gather_host = nullptr;  // pinned run-offset table of a bytes-API aggregation of archives (gather_cap words)
   size_t gather_cap = 0;
-  shelfi::EvalState* ev = nullptr;  // EvalMult / ModReduce state (eval.cpp), lazily created
+  shelfi::EvalState* ev = nullptr;  // EvalMult / ModReduce state (eval_state.cpp), lazily created
   // RCCL communicator of the multi-GPU combine (comm.cpp; ncclComm_t, opaque here)
   void* comm = nullptr;
   int comm_rank = 0, comm_world = 0;
@@ -328,7 +328,7 @@ struct ArenaPack {
   uint32_t pre[kMaxTowers];  // sum of U_t' for t' < t
   uint32_t sum;              // sum of U_t
 };
-ArenaPack arena_pack(const Params& p);                 // dev_api.cpp
+ArenaPack arena_pack(const Params& p);                 // dev_arena.cpp
 uint64_t arena_ct_words(const Params& p, uint64_t C);  // uint64 words per ciphertext of C learners
 // sum_c W_c x_c over C learners (any C: groups of 16 folded into a running sum), weight limbs
 // wl_dev [C][L][2]; rows = K * 2 * L ciphertext polynomials
@@ -469,7 +469,7 @@ void launch_partial_decrypt(const Params& p, const DeviceTables& dt, const Devic
                             uint64_t K, uint32_t towers, bool lead, uint64_t* out, void* scratch, double sigma,
                             const uint32_t key[8], uint64_t g0, hipStream_t s);
 
-// dev_api.cpp: the arena aggregation (ctx lock held, weights checked), refused-slot check;
+// dev_arena.cpp: the arena aggregation (ctx lock held, weights checked), refused-slot check;
 // call_state.cpp: weights
 void wavg_arena_enqueue(shelfi_ctx* ctx, const uint64_t* arena_dev, const float* w, size_t C, size_t K,
                         uint64_t* out_dev, hipStream_t s);
@@ -481,15 +481,11 @@ void arena_require_valid_locked(const shelfi_ctx* ctx, const uint64_t* a, size_t
 void check_wavg_weights(const float* w, size_t C, double delta);
 // comm.cpp: drop the context's RCCL communicator (if any)
 void comm_release(shelfi_ctx* ctx);
-// eval.cpp: drop the relinearization key (keys_only) or all EvalMult / ModReduce state
+// eval_state.cpp: drop the relinearization key (keys_only) or all EvalMult / ModReduce state
 void eval_release(shelfi_ctx* ctx, bool keys_only);
-// eval.cpp: install cryptodir's key-eval-mult.txt when it belongs to the loaded keys
+// eval_keys.cpp: install cryptodir's key-eval-mult.txt when it belongs to the loaded keys
 void load_evalkey_if_present(shelfi_ctx* ctx, const std::string& dir);
-// eval.cpp: NTT / CRT tables of Q_l (towers q_0 .. q_{Ll-1}) for decrypt at a level
-const DeviceTables& level_tables(shelfi_ctx* ctx, uint32_t Ll);
-// context.cpp helpers shared with eval.cpp
-void seed_to_key(uint64_t seed, uint32_t key[8]);
-void os_random(void* buf, size_t n);
+// context.cpp: refuse a call that needs keys before they are loaded
 void require_keys(const shelfi_ctx* ctx);
 
 // ---- EvalMult (ct x ct) + relinearization, ModReduce (keyswitch.hip) ----

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 import oracle as O
-from conftest import PALISADE_DIR
+from conftest import PALISADE_DIR, set_switch
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -196,3 +196,57 @@ def test_reference_keys_and_refusals():
         with pytest.raises(ValueError, match="non-finite"):
             ck.encrypt(np.array([1e9, bad]))
     assert ck.encode_redo_count() == n0  # a refusal is not a redo
+
+
+def _encrypt_chunks(inf, K, mib):
+    """shelfi_dev_encrypt's launch chains under SHELFI_DEV_CHUNK_MIB = mib: K split evenly over the fewest
+    chains whose scratch fits the budget, at encrypt_scratch_bytes(p, 1) (encrypt.hip) per ciphertext: the
+    FFT buffer, pbuf [3][L][N], me0 and ve [N], the large-value path's words, and 64."""
+    N, S, L = inf["ring_dim"], inf["batch"], inf["num_towers"]
+    per = S * 16 + 3 * L * N * 8 + N * 10 + 16 + 16 * L + 64
+    cap = max(1, (mib << 20) // per)
+    nch = -(-K // cap)
+    kc = -(-K // nch)
+    return [min(kc, K - k0) for k0 in range(0, K, kc)]
+
+
+def test_chunked_device_call_is_redone_once(tmp_path, monkeypatch):
+    """D.encrypt cut into launch chains (SHELFI_DEV_CHUNK_MIB=1) with the one large value in the last, shorter
+    chain: both passes walk the same chunks, so the ciphertexts are bit-identical to the unsplit call's and the
+    call is redone, and counted, once; the same split without the large value is not redone.  Ring 2^13 / L2
+    with 2048 slots: 496 KiB of scratch a ciphertext, two to the MiB (4096 slots would leave one, and no
+    shorter last chain)."""
+    ck = m.CKKS("ckks", 2048, 52, str(tmp_path) + os.sep, ringDim=8192, seed=71, decodeNoise=False)
+    assert ck.genCryptoContextAndKeyGen() == 1
+    inf = ck.info()
+    N, S = inf["ring_dim"], inf["batch"]
+    assert (N, inf["num_towers"], S) == (8192, 2, 2048)
+    # the smallest count cut into at least three chains, the last one shorter
+    chunks = next(c for c in (_encrypt_chunks(inf, k, 1) for k in range(3, 64)) if len(c) >= 3 and c[-1] < c[0])
+    K = sum(chunks)
+    assert chunks == [2, 2, 1] and _encrypt_chunks(inf, K, 4096) == [K]
+    n = K * S - 3
+    small = np.random.default_rng(9).uniform(-1, 1, n)
+    x = small.copy()
+    last = (K - chunks[-1]) * S  # the first slot of the last chain
+    x[last + 5] = 2.0 ** 24
+    scaled, top = _redone(small, N, S, inf["delta"])
+    assert not scaled and top <= 2 ** 61  # the earlier chains, and the call without the large value
+    scaled, top = _redone(x[last:], N, S, inf["delta"])
+    assert scaled or top > 2 ** 61
+
+    def run(v):
+        ck.set_seed(72)
+        n0 = ck.encode_redo_count()
+        ct = D.encrypt(ck, torch.from_numpy(v).cuda())
+        torch.cuda.synchronize()
+        return ct.cpu().numpy().view(np.uint64).copy(), ck.encode_redo_count() - n0
+
+    whole, redone = run(x)
+    assert redone == 1
+    set_switch(monkeypatch, "SHELFI_DEV_CHUNK_MIB", "1")
+    split, redone = run(x)
+    assert redone == 1
+    assert np.array_equal(split, whole)
+    assert run(small)[1] == 0
+    set_switch(monkeypatch, "SHELFI_DEV_CHUNK_MIB", None)
