@@ -632,10 +632,14 @@ def sub_plain(ckks, ct, pt, out=None):
 
 
 def ntt(ckks, polys, inverse: bool = False):
-    """In-place negacyclic NTT (PALISADE order) of [P][N] polys; tower = p % L."""
+    """In-place negacyclic NTT (PALISADE order) of [P][N] polys; tower = p % L.  Inputs are canonical
+    residues below their tower's modulus, outputs are canonical, and P may be any count."""
     inf = ckks.info()
     if not polys.is_cuda or not polys.is_contiguous() or polys.shape[-1] != inf["ring_dim"]:
         raise ValueError("polys must be a contiguous CUDA tensor [P][N]")
+    # the kernels transform P polynomials of 8-byte words: any other element size is a shorter buffer
+    if polys.dtype != _torch().int64 or polys.numel() % inf["ring_dim"]:
+        raise ValueError("polys must be int64 (uint64 residues), a whole number of polynomials")
     P = polys.numel() // inf["ring_dim"]
     check(_lib.load().shelfi_dev_ntt(ckks._ctx, C.c_void_p(polys.data_ptr()), P, 1 if inverse else 0,
                                      C.c_void_p(_stream_ptr(polys))), "dev_ntt")

@@ -1193,7 +1193,9 @@ void launch_decrypt(const Params& p, const DeviceTables& dt, const DeviceKeys& d
   const uint32_t blkLog = ntt_block_log(p.logN);
   const int logR = (int)(p.logN - blkLog);
   const size_t fuse_lds = (size_t)p.L * 64 * sizeof(uint64_t) << (logR > 0 ? logR : 0);
-  const bool fuse = !exact && logR > 0 && fuse_lds <= kCrtFuseLds && p.gap <= 64 &&
+  // (the fused pass has no 64-row form: logR = 6, ring 2^17 over 2^11 blocks, whose one-tower chain
+  // would fit the LDS bound, takes the unfused pair)
+  const bool fuse = !exact && logR > 0 && logR <= 5 && fuse_lds <= kCrtFuseLds && p.gap <= 64 &&
                     ((p.N >> logR) % 64) == 0;
   {
     const uint64_t P = K * p.L, nbBlocks = P << logR;

@@ -347,7 +347,9 @@ int shelfi_dev_encrypt(shelfi_ctx* ctx, const double* x_dev, size_t n, uint64_t*
 /* decrypt + decode K ciphertexts of scaling factor `scale` into n doubles (device). */
 int shelfi_dev_decrypt(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, double scale,
                        size_t n, double* out_dev, void* stream);
-/* negacyclic NTT of P polys [P][N] whose tower is (p % L) (PALISADE order). */
+/* negacyclic NTT of P polys [P][N] whose tower is (p % L) (PALISADE order).  Inputs are canonical
+ * residues below their tower's modulus, outputs are canonical, and P may be any count (not only a
+ * multiple of L; 0 is a no-op). */
 int shelfi_dev_ntt(shelfi_ctx* ctx, uint64_t* polys_dev, size_t P, int inverse, void* stream);
 
 /* ---- EvalMult (ct x ct), relinearization, ModReduce ---------- *
