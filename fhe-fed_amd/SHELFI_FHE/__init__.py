@@ -467,6 +467,11 @@ class CKKS(Scheme):
         (2048 by default); 0 after a call that enqueued none (K = 0, rotate by 0, eval_sum with n = 1)."""
         return int(self._lib.shelfi_eval_chunk_count(self._ctx))
 
+    def dot_slice_count(self) -> int:
+        """Slices the last successful device.dot of this context summed its ciphertexts in
+        (shelfi_dot_slice_count): min(16, ceil(K / SHELFI_DOT_SLICE_CTS)); a refused call leaves it."""
+        return int(self._lib.shelfi_dot_slice_count(self._ctx))
+
     # ------------------------------------------------------------ hot path --
     def _take(self, ptr: "_lib.u8p", n: int) -> bytes:
         try:

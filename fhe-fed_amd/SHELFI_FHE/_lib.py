@@ -170,6 +170,9 @@ SIGNATURES = {
     "shelfi_set_eval_key": (C.c_int, [C.c_void_p, u64p]),
     "shelfi_dev_mult": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                   C.c_void_p]),
+    "shelfi_dev_dot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                 C.c_void_p]),
+    "shelfi_dot_slice_count": (C.c_uint64, [C.c_void_p]),
     "shelfi_dev_rescale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "shelfi_dev_decrypt_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_double,
                                            C.c_size_t, C.c_void_p, C.c_void_p]),

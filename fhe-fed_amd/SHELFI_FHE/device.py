@@ -480,6 +480,32 @@ def mult(ckks, a, b, out=None):
     return out
 
 
+def dot(ckks, a, b, out=None):
+    """cc->EvalInnerProduct's body over K ciphertext pairs of the same level: sum_k a_k (x) b_k as one
+    three-component tensor, relinearized once (needs ckks.evalMultKeyGen()) -> one ciphertext
+    [1][2][l][N] whose slots hold sum_k x_k[i] y_k[i].  It decrypts to what the sum of K mult()s decrypts
+    to, with one key switch instead of K.  a is b (or the same storage) takes the squared path, reading
+    each ciphertext once.  out must overlap neither input.  Scale: scale_a * scale_b."""
+    torch = _torch()
+    _check_ct(a, ckks, any_level=True)
+    _check_ct(b, ckks, a.shape[0], any_level=True)
+    if a.shape != b.shape:
+        raise ValueError("EvalInnerProduct operands must have the same shape (same level)")
+    if b.device != a.device:
+        raise ValueError("EvalInnerProduct operands must live on the same device")
+    K, _, l, N = a.shape
+    if K == 0:  # (an empty tensor has no storage to hand the library, which refuses K = 0 by name)
+        raise ValueError("EvalInnerProduct needs at least one ciphertext pair")
+    if out is None:
+        out = torch.empty((1, 2, l, N), dtype=a.dtype, device=a.device)
+    _check_ct(out, ckks, 1, any_level=True)
+    if tuple(out.shape) != (1, 2, l, N) or out.device != a.device:
+        raise ValueError("out must be a contiguous [1][2][l][N] 64-bit tensor on a's device")
+    check(_lib.load().shelfi_dev_dot(ckks._ctx, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), K, int(l),
+                                     C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(a))), "dev_dot")
+    return out
+
+
 def rescale(ckks, ct, out=None):
     """cc->ModReduce(ct): drop the last tower, dividing by it with rounding
     ([K][2][l][N] -> [K][2][l-1][N]); scale / q_{l-1}."""

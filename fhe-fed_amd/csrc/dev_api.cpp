@@ -1,7 +1,7 @@
 // dev_api.cpp — the device API (shelfi_dev_*: device buffers in, device buffers out, the caller's
 // stream): aggregation of separate batches, encrypt / decrypt and their threshold forms, the plaintext
-// operands, and the evaluation calls (EvalMult, ModReduce, Rotate, EvalSum, EvalAdd / Sub / Negate;
-// DESIGN.md §2.11, §2.13).  The packed resident arena is dev_arena.cpp.
+// operands, and the evaluation calls (EvalMult, EvalInnerProduct, ModReduce, Rotate, EvalSum, EvalAdd / Sub /
+// Negate).  The packed resident arena is dev_arena.cpp.
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -380,6 +380,41 @@ int shelfi_dev_mult(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_de
     SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
     ctx->eval_chunk_count = chains;
   });
+}
+
+// EvalInnerProduct (dot.hip): one launch chain whatever K is -- the inputs are streamed, and the
+// scratch holds the key switch of one ciphertext and at most 16 partial tensors
+int shelfi_dev_dot(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev, size_t K, uint32_t towers,
+                   uint64_t* out_dev, void* stream) {
+  if (!ctx || !a_dev || !b_dev || !out_dev) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    DeviceGuard g(ctx->device);
+    // a chain that cannot key-switch says so, before the key it can never hold is missed
+    if (!eval_state(ctx).ks_error.empty()) throw Error{SHELFI_ERR_ARG, eval_state(ctx).ks_error};
+    if (!ctx->ev || !ctx->ev->evk)
+      throw Error{SHELFI_ERR_STATE, "no evaluation key: call evalMultKeyGen() first"};
+    LevelState& l = level(ctx, towers);
+    if (!K) throw Error{SHELFI_ERR_ARG, "EvalInnerProduct needs at least one ciphertext pair (an empty sum has no level)"};
+    // the one output ciphertext is written while nothing says which input ciphertext it would replace: apart from both
+    const uint32_t N = ctx->p.N;
+    const uint64_t ctw = 2ull * towers * N;
+    if (words_overlap(a_dev, ctw * K, out_dev, ctw) || words_overlap(b_dev, ctw * K, out_dev, ctw))
+      throw Error{SHELFI_ERR_ARG, "EvalInnerProduct output must not overlap the inputs"};
+    const KsArgs& a = l.args;
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t S = dot_slices(K, switches().dot_slice_cts);
+    void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, dot_scratch_bytes(a, S));
+    launch_dot(a, ctx->dt, l.ext, l.dtf, ctx->ev->evk, ctx->ev->evk_sh, a_dev, b_dev, K, S, out_dev, scratch, s);
+    SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
+    ctx->dot_slice_count = S;
+  });
+}
+
+uint64_t shelfi_dot_slice_count(const shelfi_ctx* ctx) {
+  if (!ctx) return 0;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return ctx->dot_slice_count;
 }
 
 int shelfi_dev_rescale(shelfi_ctx* ctx, const uint64_t* in_dev, size_t K, uint32_t towers, uint64_t* out_dev,

@@ -81,6 +81,7 @@ struct Switches {
   int arena_stager = -1;       // SHELFI_ARENA_STAGER=0|1 (-1: by upload shape)
   uint64_t dev_chunk_mib = 4096;  // SHELFI_DEV_CHUNK_MIB: device encrypt / decrypt scratch per chain
   uint64_t eval_chunk_mib = 2048;  // SHELFI_EVAL_CHUNK_MIB: EvalMult / ModReduce / Rotate / EvalSum scratch per chain
+  uint64_t dot_slice_cts = 256;   // SHELFI_DOT_SLICE_CTS: ciphertexts a slice of EvalInnerProduct (at most 16 slices)
   uint64_t wavg_chunk_mib = 0;    // SHELFI_WAVG_CHUNK_MIB: bytes-API aggregation chunk per learner group
                                   // (0: 32 MiB per learner with direct uploads, 128 per group through the ring)
   uint64_t stage_slot_mib = 16;   // SHELFI_STAGE_SLOT_MIB: pinned staging-ring slot (DMA granule)
@@ -275,6 +276,7 @@ struct shelfi_ctx {
   uint64_t decode_redo_count = 0;  // decrypt calls whose fast pass was redone exactly (shelfi_decode_redo_count)
   uint64_t encode_redo_count = 0;  // encrypt calls redone on the large-value path (shelfi_encode_redo_count)
   uint64_t eval_chunk_count = 0;   // launch chains of the last mult / rescale / rotate / eval_sum (shelfi_eval_chunk_count)
+  uint64_t dot_slice_count = 0;    // slices of the last successful dot (shelfi_dot_slice_count)
   int last_log_error = -1;       // of the last flooded decrypt, -1 if none
   bool log_error_pending = false;  // dev_flag[2] holds a newer one, read on demand (shelfi_decode_log_error)
   std::string pal_ctx_obj;       // PALISADE keys: embedded context object (§8 f1)
@@ -522,6 +524,16 @@ KsScratch ks_scratch_layout(const KsArgs& a, uint64_t K, void* scratch);
 void launch_key_switch(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,
                        const uint64_t* evk, const uint64_t* evk_sh, uint64_t K, uint64_t* out, void* scratch,
                        hipStream_t s);
+// EvalInnerProduct (dot.hip): out [1][2][Ll][N] = (c0, c1) + KeySwitch(c2) of the summed tensor
+// sum_k x_k (x) y_k over x, y [K][2][Ll][N] (x == y: the squared path, each ciphertext read once), the
+// K ciphertexts cut into S slices (1 <= S <= min(kDotMaxSlices, K)); out overlaps neither input;
+// scratch = dot_scratch_bytes(a, S).  dot_slices: S for K ciphertexts at slice_cts a slice.
+constexpr int kDotMaxSlices = 16;  // uint64 sums of 16 canonical residues (< 2^60) cannot wrap
+size_t dot_scratch_bytes(const KsArgs& a, uint32_t S);
+uint32_t dot_slices(uint64_t K, uint64_t slice_cts);
+void launch_dot(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,
+                const uint64_t* evk, const uint64_t* evk_sh, const uint64_t* x, const uint64_t* y, uint64_t K,
+                uint32_t S, uint64_t* out, void* scratch, hipStream_t s);
 // Rotation (rotate.hip): out = (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)) under the rotation key of
 // the Galois element g; ct, out [K][2][Ll][N], not overlapping; scratch = ks_scratch_bytes(.., K).
 void launch_rotate(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,

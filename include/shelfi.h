@@ -393,6 +393,21 @@ int shelfi_palisade_evalkey_rewrite(const uint8_t* file, size_t len, const uint6
  * [K][2][towers][N] in HBM (out may be a or b).  Result depth 2, scale = scale_a scale_b. */
 int shelfi_dev_mult(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev, size_t K, uint32_t towers,
                     uint64_t* out_dev, void* stream);
+/* cc->EvalInnerProduct's body (EvalMultNoRelin + EvalAddMany + Relinearize) as one call: per tower, in
+ * EVALUATION form, c0 = sum_k a_k0 b_k0, c1 = sum_k (a_k0 b_k1 + a_k1 b_k0), c2 = sum_k a_k1 b_k1 mod q_t,
+ * and out = (c0, c1) + KeySwitch(c2) under the installed evaluation key -- shelfi_dev_mult's key switch, run
+ * once for the whole batch.  a_dev, b_dev [K][2][towers][N], out_dev [1][2][towers][N] in HBM; a_dev == b_dev
+ * (the squared norm) reads each ciphertext once and gives the bits the general path gives on a copy.  Result
+ * depth 2, scale = scale_a scale_b.  No evaluation key: SHELFI_ERR_STATE.  towers outside 1..L, a NULL buffer,
+ * K = 0 (an empty sum has no operand to take a level from), out_dev overlapping either input, and a chain with
+ * num_towers + special primes > 16: SHELFI_ERR_ARG.  The K ciphertexts are summed in S = min(16, ceil(K /
+ * SHELFI_DOT_SLICE_CTS)) slices (no output bit depends on S).  Uses the context's scratch (the key switch of
+ * one ciphertext plus 3 S towers N words) and synchronises `stream` before returning. */
+int shelfi_dev_dot(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev, size_t K, uint32_t towers,
+                   uint64_t* out_dev, void* stream);
+/* slices S of the last successful shelfi_dev_dot on this context (a refused call leaves it unchanged; for
+ * tests of the split) */
+uint64_t shelfi_dot_slice_count(const shelfi_ctx* ctx);
 /* cc->ModReduce / Rescale: [K][2][towers][N] -> [K][2][towers-1][N] (no overlap), dividing by
  * q_{towers-1} with rounding; scale / q_{towers-1}. */
 int shelfi_dev_rescale(shelfi_ctx* ctx, const uint64_t* in_dev, size_t K, uint32_t towers, uint64_t* out_dev,
