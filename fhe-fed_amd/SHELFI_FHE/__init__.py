@@ -462,7 +462,7 @@ class CKKS(Scheme):
         return self._mk_add(keys, True, "multiAddEvalMultKeys")
 
     def eval_chunk_count(self) -> int:
-        """Launch chains the last successful device.mult / rescale / rotate / eval_sum of this context
+        """Launch chains the last successful device.mult / gram / rescale / rotate / eval_sum of this context
         took (shelfi_eval_chunk_count): 1 unless the batch's scratch exceeds SHELFI_EVAL_CHUNK_MIB
         (2048 by default); 0 after a call that enqueued none (K = 0, rotate by 0, eval_sum with n = 1)."""
         return int(self._lib.shelfi_eval_chunk_count(self._ctx))
@@ -471,6 +471,12 @@ class CKKS(Scheme):
         """Slices the last successful device.dot of this context summed its ciphertexts in
         (shelfi_dot_slice_count): min(16, ceil(K / SHELFI_DOT_SLICE_CTS)); a refused call leaves it."""
         return int(self._lib.shelfi_dot_slice_count(self._ctx))
+
+    def gram_slice_count(self) -> int:
+        """Slices the last successful device.gram of this context summed its ciphertexts in
+        (shelfi_gram_slice_count): min(16, ceil(K / SHELFI_GRAM_SLICE_CTS), ceil(1024 / workgroups a slice));
+        a refused call leaves it."""
+        return int(self._lib.shelfi_gram_slice_count(self._ctx))
 
     # ------------------------------------------------------------ hot path --
     def _take(self, ptr: "_lib.u8p", n: int) -> bytes:

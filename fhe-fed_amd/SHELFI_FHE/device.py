@@ -506,6 +506,77 @@ def dot(ckks, a, b, out=None):
     return out
 
 
+GRAM_MAX_BATCHES = 32  # shelfi_dev_gram: the batches' base pointers travel in the kernel arguments
+
+
+def gram_pairs(C: int):
+    """The pairs (i, j), i <= j, in the order device.gram writes them: the upper triangle, row-major;
+    (i, j) sits at i C - i (i - 1) / 2 + (j - i)."""
+    return [(i, j) for i in range(int(C)) for j in range(i, int(C))]
+
+
+def gram(ckks, batches, out=None):
+    """The Gram matrix of C batches of K ciphertexts at one level (needs ckks.evalMultKeyGen()): a batch
+    [P][2][l][N] of P = C (C + 1) / 2 ciphertexts, the one at gram_pairs(C).index((i, j)) being exactly
+    dot(ckks, batches[i], batches[j]), bit for bit -- its slots hold sum_k x_ik[s] x_jk[s] -- at one pass over
+    the inputs per tile of 2 x 2 batches and one batched key switch.  batches: a sequence of 1..32 tensors
+    [K][2][l][N] (the same tensor may appear twice), or one stacked [C][K][2][l][N] tensor.  out must overlap
+    no input.  Scale: scale^2.  rescale, eval_sum, add, sub, decrypt and partial_decrypt take the result as
+    any batch of P ciphertexts."""
+    torch = _torch()
+    if hasattr(batches, "dim"):
+        if batches.dim() != 5 or not batches.is_contiguous():
+            raise ValueError("a stacked Gram operand must be a contiguous [C][K][2][l][N] tensor")
+        batches = [batches[i] for i in range(batches.shape[0])]
+    batches = list(batches)
+    n = len(batches)
+    if not 1 <= n <= GRAM_MAX_BATCHES:
+        raise ValueError("Gram needs 1..%d batches" % GRAM_MAX_BATCHES)
+    a = batches[0]
+    _check_ct(a, ckks, any_level=True)
+    for b in batches[1:]:
+        _check_ct(b, ckks, a.shape[0], any_level=True)
+        if b.shape != a.shape:
+            raise ValueError("Gram operands must have the same shape (same level)")
+        if b.device != a.device:
+            raise ValueError("Gram operands must live on the same device")
+    K, _, l, N = a.shape
+    if K == 0:  # (an empty tensor has no storage to hand the library, which refuses K = 0 by name)
+        raise ValueError("Gram needs at least one ciphertext a batch")
+    P = n * (n + 1) // 2
+    if out is None:
+        out = torch.empty((P, 2, l, N), dtype=a.dtype, device=a.device)
+    _check_ct(out, ckks, P, any_level=True)
+    if tuple(out.shape) != (P, 2, l, N) or out.device != a.device:
+        raise ValueError("out must be a contiguous [C (C + 1) / 2][2][l][N] 64-bit tensor on the batches' device")
+    ptrs = (C.c_void_p * n)(*[b.data_ptr() for b in batches])
+    check(_lib.load().shelfi_dev_gram(ckks._ctx, ptrs, n, K, int(l), C.c_void_p(out.data_ptr()),
+                                      C.c_void_p(_stream_ptr(a))), "dev_gram")
+    return out
+
+
+def gram_sq_distances(ckks, G, n: int, out=None):
+    """Krum's input from gram()'s result G [P][2][l][N] over n batches: the n (n - 1) / 2 ciphertexts
+    G_ii + G_jj - 2 G_ij of ||u_i - u_j||^2 for i < j, in gram_pairs(n)'s order without the diagonal.  Index
+    gathers and the existing add / sub: no key, no new level, G's scale."""
+    torch = _torch()
+    n = int(n)
+    _check_ct(G, ckks, n * (n + 1) // 2, any_level=True)
+    if n < 2:
+        raise ValueError("squared distances need at least two batches")
+    pairs = gram_pairs(n)
+    at = {p: k for k, p in enumerate(pairs)}
+    off = [p for p in pairs if p[0] != p[1]]
+
+    def take(idx):
+        return G.index_select(0, torch.tensor(idx, dtype=torch.int64, device=G.device))
+
+    ij = take([at[p] for p in off])
+    out = add(ckks, take([at[(i, i)] for i, _ in off]), take([at[(j, j)] for _, j in off]), out=out)
+    sub(ckks, out, ij, out=out)
+    return sub(ckks, out, ij, out=out)
+
+
 def rescale(ckks, ct, out=None):
     """cc->ModReduce(ct): drop the last tower, dividing by it with rounding
     ([K][2][l][N] -> [K][2][l-1][N]); scale / q_{l-1}."""

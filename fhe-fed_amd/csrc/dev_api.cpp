@@ -1,7 +1,7 @@
 // dev_api.cpp — the device API (shelfi_dev_*: device buffers in, device buffers out, the caller's
 // stream): aggregation of separate batches, encrypt / decrypt and their threshold forms, the plaintext
-// operands, and the evaluation calls (EvalMult, EvalInnerProduct, ModReduce, Rotate, EvalSum, EvalAdd / Sub /
-// Negate).  The packed resident arena is dev_arena.cpp.
+// operands, and the evaluation calls (EvalMult, EvalInnerProduct, the Gram matrix, ModReduce, Rotate, EvalSum,
+// EvalAdd / Sub / Negate).  The packed resident arena is dev_arena.cpp.
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -415,6 +415,53 @@ uint64_t shelfi_dot_slice_count(const shelfi_ctx* ctx) {
   if (!ctx) return 0;
   std::lock_guard<std::mutex> lk(ctx->mu);
   return ctx->dot_slice_count;
+}
+
+// The Gram matrix (gram.hip): the tiles of pairs cut into chains under SHELFI_EVAL_CHUNK_MIB, a
+// chain the partial pass over its tiles, their reduction and one key switch of its pairs
+int shelfi_dev_gram(shelfi_ctx* ctx, const uint64_t* const* batches_dev, size_t C, size_t K, uint32_t towers,
+                    uint64_t* out_dev, void* stream) {
+  if (!ctx || !batches_dev || !out_dev) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    if (C < 1 || C > (size_t)kGramMaxLearners) throw Error{SHELFI_ERR_ARG, "Gram needs 1..32 batches"};
+    for (size_t i = 0; i < C; ++i)
+      if (!batches_dev[i]) throw Error{SHELFI_ERR_ARG, "Gram: null batch"};
+    DeviceGuard g(ctx->device);
+    // a chain that cannot key-switch says so, before the key it can never hold is missed
+    if (!eval_state(ctx).ks_error.empty()) throw Error{SHELFI_ERR_ARG, eval_state(ctx).ks_error};
+    if (!ctx->ev || !ctx->ev->evk)
+      throw Error{SHELFI_ERR_STATE, "no evaluation key: call evalMultKeyGen() first"};
+    LevelState& l = level(ctx, towers);
+    if (!K) throw Error{SHELFI_ERR_ARG, "Gram needs at least one ciphertext a batch (an empty sum has no level)"};
+    // every input is read until the last chain's partial pass: the output lies apart from all of them
+    const uint32_t N = ctx->p.N;
+    const uint64_t ctw = 2ull * towers * N, P = gram_pairs(C);
+    for (size_t i = 0; i < C; ++i)
+      if (words_overlap(batches_dev[i], ctw * K, out_dev, ctw * P))
+        throw Error{SHELFI_ERR_ARG, "Gram output must not overlap the inputs"};
+    const KsArgs& a = l.args;
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t S = gram_slices(C, K, a.Ll, a.logN, switches().gram_slice_cts);
+    constexpr uint64_t tile_pairs = (uint64_t)kGramTile * kGramTile;  // (a diagonal or ragged tile holds fewer)
+    const auto bytes_of = [&](uint64_t tc) { return gram_scratch_bytes(a, S, std::min(P, tc * tile_pairs)); };
+    const uint64_t chains =
+        for_chunks(ctx, gram_tiles(C), switches().eval_chunk_mib, bytes_of, [&](uint64_t t0, uint64_t tc, void* scratch) {
+          launch_gram(a, ctx->dt, l.ext, l.dtf, ctx->ev->evk, ctx->ev->evk_sh, batches_dev, (uint32_t)C, t0, tc, K, S,
+                      out_dev, scratch, s);
+        });
+    SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
+    ctx->eval_chunk_count = chains;
+    ctx->gram_slice_count = S;
+  });
+}
+
+size_t shelfi_gram_pairs(size_t C) { return (size_t)gram_pairs(C); }
+
+uint64_t shelfi_gram_slice_count(const shelfi_ctx* ctx) {
+  if (!ctx) return 0;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return ctx->gram_slice_count;
 }
 
 int shelfi_dev_rescale(shelfi_ctx* ctx, const uint64_t* in_dev, size_t K, uint32_t towers, uint64_t* out_dev,

@@ -16,42 +16,10 @@
 
 #include <algorithm>
 
-#include "dev_common.h"
+#include "dot_dev.h"
 #include "shelfi_internal.h"
 
 namespace shelfi {
-
-typedef unsigned __int128 du128;
-
-// acc (ANY 128-bit value) -> [0, q): acc = hi 2^64 + lo; shoup_mul reduces hi r64 for any 64-bit hi
-// (r64 = 2^64 mod q < q with its Shoup companion: x w - floor(x w' / 2^64) q < 2q for every x < 2^64),
-// red64 reduces any 64-bit lo, and addmod joins two canonical residues.  keyswitch.hip's red128 is
-// this same arithmetic; its "< 2^124" comment describes its callers' sums, not a limit of the
-// reduction.  Restated here so that the fold interval below rests on a statement made in this file.
-__device__ __forceinline__ uint64_t dot_red128(du128 acc, const TowerConst& c) {
-  const uint64_t hi = (uint64_t)(acc >> 64), lo = (uint64_t)acc;
-  return addmod(shoup_mul(hi, c.r64, c.r64_shoup, c.q), red64(lo, c.q, c.one_shoup), c.q);
-}
-
-// Fold interval G, in ciphertexts, for a tower of b = bitlength(q) bits.  The reduction takes any
-// 128-bit value, so the only limit is that the accumulator itself must not wrap.  An accumulator
-// starts a run at r < q (the previous fold's residue, carried in the accumulator) and takes P
-// products of canonical residues, each <= (q - 1)^2 <= (2^b - 2)^2 = 2^2b - 2^(b+2) + 4:
-//   r + P (q - 1)^2  <  2^b + 2^(e+2b) - 2^(e+b+2) + 2^(e+2)        with P = 2^e
-// With e = 128 - 2b that is 2^128 - (2^(130-b) - 2^(130-2b) - 2^b) < 2^128 whenever
-// 2^b + 2^(130-2b) <= 2^(130-b), true for 44 <= b <= 63; with e capped at 32 (b < 48) the sum stays
-// below 2^(33+2b) < 2^128.  c1 takes two products per ciphertext (the squared path doubles one), c0
-// and c2 one, so a run may hold G = P / 2 ciphertexts: 128 on a 60-bit tower, 2^31 from 48 bits down.
-__device__ __forceinline__ uint64_t dot_fold_interval(uint64_t q) {
-  const int b = 64 - __builtin_clzll(q);
-  const int e = max(min(128 - 2 * b, 32), 1);  // (b <= 60 in every chain the library builds)
-  return 1ull << (e - 1);
-}
-
-__device__ __forceinline__ ulonglong2 ld_pair(const uint64_t* p) {
-  const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-  return make_ulonglong2(((uint64_t)v.y << 32) | v.x, ((uint64_t)v.w << 32) | v.z);
-}
 
 // Grid (512-coefficient block, tower, slice); one thread = 2 adjacent coefficients (16-byte loads), the
 // tower block-uniform so its constants sit in SGPRs (wavg_kernel's arrangement).  The workgroup walks
@@ -127,10 +95,8 @@ __global__ __launch_bounds__(256) void dot_partial_kernel(const uint64_t* __rest
   *reinterpret_cast<ulonglong2*>(o + 2 * poly) = make_ulonglong2((uint64_t)c2x, (uint64_t)c2y);
 }
 
-// One workgroup per (tower, NTT block), ks_tensor_intt_kernel's geometry with K = 1: the S <= 16
-// canonical partials of every residue are summed as plain uint64 (16 q < 2^64 for q < 2^60: the
-// argument of threshold fusion and mk_key_add_kernel) and folded by one red64; c0 and c1 go to out,
-// c2 to d2e (EVALUATION) and into LDS, where the first inverse stages run into d2c.
+// One workgroup per (tower, NTT block), ks_tensor_intt_kernel's geometry with K = 1: dot_reduce_block on
+// part [S][3][Ll][N].
 __global__ __launch_bounds__(256) void dot_reduce_intt_kernel(const uint64_t* __restrict__ part, uint32_t S,
                                                               uint32_t Ll, uint32_t logN, uint32_t blkLog,
                                                               const uint64_t* __restrict__ itw,
@@ -140,38 +106,11 @@ __global__ __launch_bounds__(256) void dot_reduce_intt_kernel(const uint64_t* __
                                                               uint64_t* __restrict__ d2e,
                                                               uint64_t* __restrict__ d2c) {
   extern __shared__ __attribute__((aligned(16))) uint64_t sm[];
-  const uint32_t N = 1u << logN, blk = 1u << blkLog, sh = logN - blkLog;
+  const uint32_t sh = logN - blkLog;
   const uint32_t t = blockIdx.x >> sh, b = blockIdx.x & ((1u << sh) - 1);
-  const TowerConst c = tq[t];
-  const uint64_t q = c.q, osh = c.one_shoup;
   const uint64_t poly = (uint64_t)Ll << logN;
-  const uint64_t off = ((uint64_t)t << logN) + ((uint64_t)b << blkLog);
-  const ulonglong2* P = reinterpret_cast<const ulonglong2*>(part + off);
-  const uint64_t cs = poly / 2, ss = 3 * cs;  // component and slice strides in 16-byte pairs
-  ulonglong2* O0 = reinterpret_cast<ulonglong2*>(out + off);
-  ulonglong2* O1 = reinterpret_cast<ulonglong2*>(out + poly + off);
-  ulonglong2* E2 = reinterpret_cast<ulonglong2*>(d2e + off);
-  for (uint32_t p = threadIdx.x; p < blk / 2; p += 256) {
-    ulonglong2 r0 = make_ulonglong2(0, 0), r1 = r0, r2 = r0;
-    for (uint32_t s = 0; s < S; ++s) {
-      const ulonglong2 v0 = P[s * ss + p], v1 = P[s * ss + cs + p], v2 = P[s * ss + 2 * cs + p];
-      r0.x += v0.x;
-      r0.y += v0.y;
-      r1.x += v1.x;
-      r1.y += v1.y;
-      r2.x += v2.x;
-      r2.y += v2.y;
-    }
-    r0 = make_ulonglong2(red64(r0.x, q, osh), red64(r0.y, q, osh));
-    r1 = make_ulonglong2(red64(r1.x, q, osh), red64(r1.y, q, osh));
-    r2 = make_ulonglong2(red64(r2.x, q, osh), red64(r2.y, q, osh));
-    O0[p] = r0;
-    O1[p] = r1;
-    E2[p] = r2;
-    lds_put2(sm, p, r2);
-  }
-  __syncthreads();
-  ks_intt_block_out(sm, blkLog, b, logN, itw + (uint64_t)t * N, itwp + (uint64_t)t * N, c, d2c + off);
+  dot_reduce_block(sm, part, part + poly, 3 * poly, part + 2 * poly, 3 * poly, S, t, b, logN, blkLog, itw, itwp, tq[t], out,
+                   out + poly, d2e, d2c);
 }
 
 // scratch: the key switch's for one ciphertext (rounded up to 64 bytes) | part [S][3][Ll][N]

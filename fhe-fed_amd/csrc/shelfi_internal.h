@@ -82,6 +82,7 @@ struct Switches {
   uint64_t dev_chunk_mib = 4096;  // SHELFI_DEV_CHUNK_MIB: device encrypt / decrypt scratch per chain
   uint64_t eval_chunk_mib = 2048;  // SHELFI_EVAL_CHUNK_MIB: EvalMult / ModReduce / Rotate / EvalSum scratch per chain
   uint64_t dot_slice_cts = 256;   // SHELFI_DOT_SLICE_CTS: ciphertexts a slice of EvalInnerProduct (at most 16 slices)
+  uint64_t gram_slice_cts = 256;  // SHELFI_GRAM_SLICE_CTS: the same for the Gram matrix, sliced only while its tiles leave the machine idle
   uint64_t wavg_chunk_mib = 0;    // SHELFI_WAVG_CHUNK_MIB: bytes-API aggregation chunk per learner group
                                   // (0: 32 MiB per learner with direct uploads, 128 per group through the ring)
   uint64_t stage_slot_mib = 16;   // SHELFI_STAGE_SLOT_MIB: pinned staging-ring slot (DMA granule)
@@ -275,8 +276,9 @@ struct shelfi_ctx {
   int decode_exact = 0;          // shelfi_set_decode_exact: every decrypt over every tower, exact CRT
   uint64_t decode_redo_count = 0;  // decrypt calls whose fast pass was redone exactly (shelfi_decode_redo_count)
   uint64_t encode_redo_count = 0;  // encrypt calls redone on the large-value path (shelfi_encode_redo_count)
-  uint64_t eval_chunk_count = 0;   // launch chains of the last mult / rescale / rotate / eval_sum (shelfi_eval_chunk_count)
+  uint64_t eval_chunk_count = 0;   // launch chains of the last mult / gram / rescale / rotate / eval_sum (shelfi_eval_chunk_count)
   uint64_t dot_slice_count = 0;    // slices of the last successful dot (shelfi_dot_slice_count)
+  uint64_t gram_slice_count = 0;   // slices of the last successful gram (shelfi_gram_slice_count)
   int last_log_error = -1;       // of the last flooded decrypt, -1 if none
   bool log_error_pending = false;  // dev_flag[2] holds a newer one, read on demand (shelfi_decode_log_error)
   std::string pal_ctx_obj;       // PALISADE keys: embedded context object (§8 f1)
@@ -534,6 +536,22 @@ uint32_t dot_slices(uint64_t K, uint64_t slice_cts);
 void launch_dot(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,
                 const uint64_t* evk, const uint64_t* evk_sh, const uint64_t* x, const uint64_t* y, uint64_t K,
                 uint32_t S, uint64_t* out, void* scratch, hipStream_t s);
+// The Gram matrix (gram.hip): out [C (C + 1) / 2][2][Ll][N], out[p(i, j)] = launch_dot's result on (u[i], u[j])
+// for i <= j, the upper triangle row-major; u: C <= kGramMaxLearners device batches [K][2][Ll][N] (a batch may
+// appear twice), out overlapping none.  The pairs are worked in tiles of kGramTile x kGramTile learners,
+// gram_tiles(C) of them; one call runs the chain of tiles [t0, t0 + tc) -- its partial sums in S slices, their
+// reduction and ONE key switch of the chain's pairs -- with scratch = gram_scratch_bytes(a, S, pairs of the
+// chain), at most kGramTile^2 pairs a tile.  gram_slices: S for the whole call.
+constexpr int kGramMaxLearners = 32;  // 32 base pointers by value in the kernel arguments
+constexpr int kGramTile = 2;
+constexpr uint64_t kGramFillGroups = 1024;  // workgroups of the partial pass below which a call is sliced over K
+uint64_t gram_pairs(uint64_t C);
+uint64_t gram_tiles(uint64_t C);
+uint32_t gram_slices(uint64_t C, uint64_t K, uint32_t Ll, uint32_t logN, uint64_t slice_cts);
+size_t gram_scratch_bytes(const KsArgs& a, uint32_t S, uint64_t kc);
+void launch_gram(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,
+                 const uint64_t* evk, const uint64_t* evk_sh, const uint64_t* const* u, uint32_t C, uint64_t t0,
+                 uint64_t tc, uint64_t K, uint32_t S, uint64_t* out, void* scratch, hipStream_t s);
 // Rotation (rotate.hip): out = (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)) under the rotation key of
 // the Galois element g; ct, out [K][2][Ll][N], not overlapping; scratch = ks_scratch_bytes(.., K).
 void launch_rotate(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,

@@ -408,6 +408,27 @@ int shelfi_dev_dot(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev
 /* slices S of the last successful shelfi_dev_dot on this context (a refused call leaves it unchanged; for
  * tests of the split) */
 uint64_t shelfi_dot_slice_count(const shelfi_ctx* ctx);
+/* The Gram matrix of C batches of K ciphertexts, all at one level: out_dev [P][2][towers][N], P = C (C + 1) / 2,
+ * holds for every i <= j, at p(i, j) = i C - i (i - 1) / 2 + (j - i) (the upper triangle, row-major), exactly
+ * the ciphertext shelfi_dev_dot gives on (batch i, batch j), bit for bit: the pairwise inner products robust
+ * aggregation rules need (Krum's distances G_ii + G_jj - 2 G_ij, cosine screening), at one pass over the
+ * inputs per tile of 2 x 2 learners and one batched key switch instead of P single ones.  batches_dev: a HOST
+ * array of C device pointers [K][2][towers][N] (the same batch may appear twice); the result is a batch of P
+ * ordinary ciphertexts of depth 2 and scale = scale^2 for shelfi_dev_rescale, _eval_sum, _add, _sub and the
+ * decrypt calls.  No evaluation key: SHELFI_ERR_STATE.  C outside 1..32, K = 0, towers outside 1..L, a NULL
+ * pointer, out_dev overlapping any input, and a chain with num_towers + special primes > 16: SHELFI_ERR_ARG.
+ * The tiles are cut into launch chains under SHELFI_EVAL_CHUNK_MIB (shelfi_eval_chunk_count reports them);
+ * the K ciphertexts are summed in S = min(16, ceil(K / SHELFI_GRAM_SLICE_CTS), ceil(1024 / G)) slices, G =
+ * ceil(C / 2) (ceil(C / 2) + 1) / 2 tiles x towers x max(1, N / 512) workgroups a slice: a call is sliced only
+ * while its tiles alone leave the machine idle.  No output bit depends on the chains or on S.  Uses the
+ * context's scratch and synchronises `stream` before returning. */
+int shelfi_dev_gram(shelfi_ctx* ctx, const uint64_t* const* batches_dev, size_t C, size_t K, uint32_t towers,
+                    uint64_t* out_dev, void* stream);
+/* C (C + 1) / 2: the ciphertexts shelfi_dev_gram writes for C batches */
+size_t shelfi_gram_pairs(size_t C);
+/* slices S of the last successful shelfi_dev_gram on this context (a refused call leaves it unchanged; for
+ * tests of the split) */
+uint64_t shelfi_gram_slice_count(const shelfi_ctx* ctx);
 /* cc->ModReduce / Rescale: [K][2][towers][N] -> [K][2][towers-1][N] (no overlap), dividing by
  * q_{towers-1} with rounding; scale / q_{towers-1}. */
 int shelfi_dev_rescale(shelfi_ctx* ctx, const uint64_t* in_dev, size_t K, uint32_t towers, uint64_t* out_dev,
@@ -460,7 +481,7 @@ int shelfi_dev_rotate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_
 int shelfi_dev_eval_sum(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, uint32_t n,
                         uint64_t* out_dev, void* stream);
 /* The number of launch chains (chunks of the batch, each within the SHELFI_EVAL_CHUNK_MIB scratch budget,
- * 2048 by default) the last successful shelfi_dev_mult, shelfi_dev_rescale, shelfi_dev_rotate or
+ * 2048 by default) the last successful shelfi_dev_mult, shelfi_dev_gram, shelfi_dev_rescale, shelfi_dev_rotate or
  * shelfi_dev_eval_sum on this context took.  0 after a call that enqueued no chain (K = 0, index 0,
  * n = 1); a refused call leaves it unchanged.  For tests of the chunking. */
 uint64_t shelfi_eval_chunk_count(const shelfi_ctx* ctx);
