@@ -478,6 +478,12 @@ class CKKS(Scheme):
         a refused call leaves it."""
         return int(self._lib.shelfi_gram_slice_count(self._ctx))
 
+    def dotp_slice_count(self) -> int:
+        """Slices the last successful device.project / dot_plain / pack_slots of this context summed its
+        ciphertexts in (shelfi_dotp_slice_count): min(16, ceil(K / SHELFI_DOTP_SLICE_CTS), ceil(1024 /
+        workgroups a slice)), lowered until the partial sums fit SHELFI_EVAL_CHUNK_MIB; a refused call leaves it."""
+        return int(self._lib.shelfi_dotp_slice_count(self._ctx))
+
     # ------------------------------------------------------------ hot path --
     def _take(self, ptr: "_lib.u8p", n: int) -> bytes:
         try:

@@ -177,6 +177,9 @@ SIGNATURES = {
                                   C.c_void_p]),
     "shelfi_gram_pairs": (C.c_size_t, [C.c_size_t]),
     "shelfi_gram_slice_count": (C.c_uint64, [C.c_void_p]),
+    "shelfi_dev_project": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "shelfi_dotp_slice_count": (C.c_uint64, [C.c_void_p]),
     "shelfi_dev_rescale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "shelfi_dev_decrypt_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_double,
                                            C.c_size_t, C.c_void_p, C.c_void_p]),

@@ -728,6 +728,100 @@ def sub_plain(ckks, ct, pt, out=None):
     return _plain_op(_lib.load().shelfi_dev_sub_plain, "dev_sub_plain", ckks, ct, pt, out)
 
 
+PROJECT_MAX_BATCHES = 32  # shelfi_dev_project: as GRAM_MAX_BATCHES, for the ciphertext and the plaintext side
+
+
+def project(ckks, batches, pts, out=None):
+    """cc->EvalInnerProduct(ct, pt) for every pair of C ciphertext batches and R plaintext batches at one level:
+    a batch [C R][2][l][N] whose entry c R + r is sum_k batches[c][k] (.) pts[r][k] in both components -- its
+    slots hold sum_k x_ck[s] g_rk[s], the projection of update c on the known vector r before the sum over slots
+    (rescale, then eval_sum).  Needs no key of any kind.  batches: a sequence of 1..32 tensors [K][2][l][N] (the
+    same tensor may appear twice), or one stacked [C][K][2][l][N] tensor; pts: [R][K][l][N] with 1 <= R <= 32, or
+    [K][l][N] for R = 1, as device.encode writes them.  out must overlap no input.  Scale: scale_ct * scale_pt.
+    At C = R = K = 1 the result is mult_plain's, bit for bit."""
+    torch = _torch()
+    if hasattr(batches, "dim"):
+        if batches.dim() != 5 or not batches.is_contiguous():
+            raise ValueError("a stacked EvalInnerProduct operand must be a contiguous [C][K][2][l][N] tensor")
+        batches = [batches[i] for i in range(batches.shape[0])]
+    batches = list(batches)
+    n = len(batches)
+    if not 1 <= n <= PROJECT_MAX_BATCHES:
+        raise ValueError("EvalInnerProduct(ct, pt) needs 1..%d ciphertext batches" % PROJECT_MAX_BATCHES)
+    a = batches[0]
+    _check_ct(a, ckks, any_level=True)
+    for b in batches[1:]:
+        _check_ct(b, ckks, a.shape[0], any_level=True)
+        if b.shape != a.shape:
+            raise ValueError("EvalInnerProduct(ct, pt) operands must have the same shape (same level)")
+        if b.device != a.device:
+            raise ValueError("EvalInnerProduct(ct, pt) operands must live on the same device")
+    K, _, l, N = a.shape
+    if K == 0:  # (an empty tensor has no storage to hand the library, which refuses K = 0 by name)
+        raise ValueError("EvalInnerProduct(ct, pt) needs at least one ciphertext a batch")
+    if not hasattr(pts, "dim") or not pts.is_cuda or not pts.is_contiguous() or pts.element_size() != 8 or pts.device != a.device:
+        raise ValueError("plaintext tensors must be contiguous 64-bit CUDA tensors on the ciphertexts' device")
+    sh = tuple(pts.shape)
+    if len(sh) == 3:  # one plaintext batch [K][l][N]
+        sh = (1,) + sh
+    if len(sh) != 4 or sh[1:] != (K, l, N):
+        raise ValueError("plaintext tensor must have shape [R][K][towers][N] = [R][%d][%d][%d], or hold one batch"
+                         % (K, l, N))
+    R = sh[0]
+    if not 1 <= R <= PROJECT_MAX_BATCHES:
+        raise ValueError("EvalInnerProduct(ct, pt) needs 1..%d plaintext batches" % PROJECT_MAX_BATCHES)
+    if out is None:
+        out = torch.empty((n * R, 2, l, N), dtype=a.dtype, device=a.device)
+    _check_ct(out, ckks, n * R, any_level=True)
+    if tuple(out.shape) != (n * R, 2, l, N) or out.device != a.device:
+        raise ValueError("out must be a contiguous [C R][2][l][N] 64-bit tensor on the batches' device")
+    ptrs = (C.c_void_p * n)(*[b.data_ptr() for b in batches])
+    check(_lib.load().shelfi_dev_project(ckks._ctx, ptrs, n, C.c_void_p(pts.data_ptr()), R, K, int(l),
+                                         C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(a))), "dev_project")
+    return out
+
+
+def dot_plain(ckks, ct, pt, out=None):
+    """cc->EvalInnerProduct(ct, pt): sum_k ct[k] (.) pt[k] over K ciphertexts [K][2][l][N] and K plaintexts
+    [K][l][N] -> one ciphertext [1][2][l][N]; project() at C = R = 1."""
+    if hasattr(pt, "dim") and pt.dim() != 3:
+        raise ValueError("plaintext tensor must have shape [K][towers][N]")
+    return project(ckks, [ct], pt, out=out)
+
+
+def _one_hots(ckks, l: int, P: int, device):
+    """The P one-hot slot vectors e_p as plaintexts [P][l][N] at scale q[l - 1], cached on the context per
+    (l, P, device) and parameter generation."""
+    torch = _torch()
+    gen = getattr(ckks, "_params_gen", 0)
+    cache = getattr(ckks, "_dev_one_hots", None)
+    if cache is None or cache[0] != gen:
+        cache = ckks._dev_one_hots = (gen, {})
+    key = (int(l), int(P), str(device))
+    if key not in cache[1]:
+        inf = ckks.info()
+        B = inf["batch"]
+        x = torch.zeros(P * B, dtype=torch.float64, device=device)
+        x[torch.arange(P, device=device) * (B + 1)] = 1.0
+        cache[1][key] = encode(ckks, x, towers=l, scale=float(inf["moduli"][l - 1]))
+    return cache[1][key]
+
+
+def pack_slots(ckks, cts, out=None):
+    """P ciphertexts that each hold one number in every slot (eval_sum's output: the entries of a Gram matrix,
+    projections) -> ONE ciphertext [1][2][l-1][N] whose slot p holds slot p of cts[p], p < P, and 0 elsewhere:
+    sum_p cts[p] (.) e_p with the one-hot plaintexts e_p encoded at scale q[l - 1] (dot_plain), then rescale --
+    one decrypt, or one partial decryption a party, opens all P numbers.  cts: [P][2][l][N], 1 <= P <= batch,
+    l >= 2.  Needs no key; the scale stays the inputs' own; one level is spent."""
+    _check_ct(cts, ckks, any_level=True)
+    P, _, l, N = cts.shape
+    if l < 2:
+        raise ValueError("pack_slots needs at least 2 towers (it ends in a ModReduce)")
+    if not 1 <= P <= ckks.info()["batch"]:
+        raise ValueError("pack_slots takes 1..batch ciphertexts, one a slot")
+    return rescale(ckks, dot_plain(ckks, cts, _one_hots(ckks, l, P, cts.device)), out=out)
+
+
 def ntt(ckks, polys, inverse: bool = False):
     """In-place negacyclic NTT (PALISADE order) of [P][N] polys; tower = p % L.  Inputs are canonical
     residues below their tower's modulus, outputs are canonical, and P may be any count."""

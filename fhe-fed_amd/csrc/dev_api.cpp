@@ -1,7 +1,7 @@
 // dev_api.cpp — the device API (shelfi_dev_*: device buffers in, device buffers out, the caller's
 // stream): aggregation of separate batches, encrypt / decrypt and their threshold forms, the plaintext
 // operands, and the evaluation calls (EvalMult, EvalInnerProduct, the Gram matrix, ModReduce, Rotate, EvalSum,
-// EvalAdd / Sub / Negate).  The packed resident arena is dev_arena.cpp.
+// EvalInnerProduct(ct, pt), EvalAdd / Sub / Negate).  The packed resident arena is dev_arena.cpp.
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -462,6 +462,41 @@ uint64_t shelfi_gram_slice_count(const shelfi_ctx* ctx) {
   if (!ctx) return 0;
   std::lock_guard<std::mutex> lk(ctx->mu);
   return ctx->gram_slice_count;
+}
+
+// EvalInnerProduct(ct, pt) (dotp.hip): no key and one launch chain whatever C, R and K are -- the
+// inputs are streamed; the slices' partial sums, when there are any, are held to the SHELFI_EVAL_CHUNK_MIB budget
+int shelfi_dev_project(shelfi_ctx* ctx, const uint64_t* const* batches_dev, size_t C, const uint64_t* pts_dev,
+                       size_t R, size_t K, uint32_t towers, uint64_t* out_dev, void* stream) {
+  if (!ctx || !batches_dev || !pts_dev || !out_dev) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    if (C < 1 || C > (size_t)kDotpMaxBatches) throw Error{SHELFI_ERR_ARG, "EvalInnerProduct(ct, pt) needs 1..32 ciphertext batches"};
+    if (R < 1 || R > (size_t)kDotpMaxBatches) throw Error{SHELFI_ERR_ARG, "EvalInnerProduct(ct, pt) needs 1..32 plaintext batches"};
+    for (size_t i = 0; i < C; ++i)
+      if (!batches_dev[i]) throw Error{SHELFI_ERR_ARG, "EvalInnerProduct(ct, pt): null batch"};
+    const Params& p = ctx->p;
+    require_towers(p, towers);
+    if (!K) throw Error{SHELFI_ERR_ARG, "EvalInnerProduct(ct, pt) needs at least one ciphertext a batch (an empty sum has no level)"};
+    // every input is read until the last workgroup ends: the output lies apart from all of them
+    const uint64_t ptw = (uint64_t)towers * p.N, ctw = 2 * ptw, ow = ctw * C * R;
+    bool apart = !words_overlap(pts_dev, ptw * K * R, out_dev, ow);
+    for (size_t i = 0; i < C; ++i) apart = apart && !words_overlap(batches_dev[i], ctw * K, out_dev, ow);
+    if (!apart) throw Error{SHELFI_ERR_ARG, "EvalInnerProduct(ct, pt) output must not overlap the inputs"};
+    DeviceGuard g(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t S = dotp_slices(C, R, K, towers, p.logN, switches().dotp_slice_cts, switches().eval_chunk_mib << 20);
+    void* scratch = S > 1 ? ensure(ctx->scratch, ctx->scratch_bytes, dotp_scratch_bytes(C, R, towers, p.logN, S)) : nullptr;
+    launch_dotp(batches_dev, (uint32_t)C, pts_dev, (uint32_t)R, K, S, towers, p.logN, ctx->dt.tc, out_dev, scratch, s);
+    if (S > 1) SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
+    ctx->dotp_slice_count = S;
+  });
+}
+
+uint64_t shelfi_dotp_slice_count(const shelfi_ctx* ctx) {
+  if (!ctx) return 0;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return ctx->dotp_slice_count;
 }
 
 int shelfi_dev_rescale(shelfi_ctx* ctx, const uint64_t* in_dev, size_t K, uint32_t towers, uint64_t* out_dev,

@@ -83,6 +83,7 @@ struct Switches {
   uint64_t eval_chunk_mib = 2048;  // SHELFI_EVAL_CHUNK_MIB: EvalMult / ModReduce / Rotate / EvalSum scratch per chain
   uint64_t dot_slice_cts = 256;   // SHELFI_DOT_SLICE_CTS: ciphertexts a slice of EvalInnerProduct (at most 16 slices)
   uint64_t gram_slice_cts = 256;  // SHELFI_GRAM_SLICE_CTS: the same for the Gram matrix, sliced only while its tiles leave the machine idle
+  uint64_t dotp_slice_cts = 256;  // SHELFI_DOTP_SLICE_CTS: the same for EvalInnerProduct(ct, pt), also held to the SHELFI_EVAL_CHUNK_MIB budget
   uint64_t wavg_chunk_mib = 0;    // SHELFI_WAVG_CHUNK_MIB: bytes-API aggregation chunk per learner group
                                   // (0: 32 MiB per learner with direct uploads, 128 per group through the ring)
   uint64_t stage_slot_mib = 16;   // SHELFI_STAGE_SLOT_MIB: pinned staging-ring slot (DMA granule)
@@ -279,6 +280,7 @@ struct shelfi_ctx {
   uint64_t eval_chunk_count = 0;   // launch chains of the last mult / gram / rescale / rotate / eval_sum (shelfi_eval_chunk_count)
   uint64_t dot_slice_count = 0;    // slices of the last successful dot (shelfi_dot_slice_count)
   uint64_t gram_slice_count = 0;   // slices of the last successful gram (shelfi_gram_slice_count)
+  uint64_t dotp_slice_count = 0;   // slices of the last successful project (shelfi_dotp_slice_count)
   int last_log_error = -1;       // of the last flooded decrypt, -1 if none
   bool log_error_pending = false;  // dev_flag[2] holds a newer one, read on demand (shelfi_decode_log_error)
   std::string pal_ctx_obj;       // PALISADE keys: embedded context object (§8 f1)
@@ -552,6 +554,19 @@ size_t gram_scratch_bytes(const KsArgs& a, uint32_t S, uint64_t kc);
 void launch_gram(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,
                  const uint64_t* evk, const uint64_t* evk_sh, const uint64_t* const* u, uint32_t C, uint64_t t0,
                  uint64_t tc, uint64_t K, uint32_t S, uint64_t* out, void* scratch, hipStream_t s);
+// EvalInnerProduct(ct, pt) (dotp.hip): out [C R][2][Ll][N], out[c R + r] = sum_k u[c][k] (.) pts[r][k] in both
+// components, canonical; u: C <= kDotpMaxBatches device batches [K][2][Ll][N] (a batch may appear twice), pts
+// [R][K][Ll][N] with R <= kDotpMaxBatches, out overlapping none; no key.  The K ciphertexts are cut into S slices
+// (1 <= S <= min(kDotMaxSlices, K)): S = 1 writes out directly and takes no scratch, S > 1 sums partials
+// [S][C R][2][Ll][N] = dotp_scratch_bytes.  dotp_slices: S for a call (gram's rule over dotp_tiles workgroup
+// tiles, lowered until the partials fit budget_bytes).
+constexpr int kDotpMaxBatches = 32;  // 32 base pointers by value in the kernel arguments
+uint64_t dotp_tiles(uint64_t C, uint64_t R);
+size_t dotp_scratch_bytes(uint64_t C, uint64_t R, uint32_t Ll, uint32_t logN, uint32_t S);
+uint32_t dotp_slices(uint64_t C, uint64_t R, uint64_t K, uint32_t Ll, uint32_t logN, uint64_t slice_cts,
+                     uint64_t budget_bytes);
+void launch_dotp(const uint64_t* const* u, uint32_t C, const uint64_t* pts, uint32_t R, uint64_t K, uint32_t S,
+                 uint32_t Ll, uint32_t logN, const TowerConst* tq, uint64_t* out, void* scratch, hipStream_t s);
 // Rotation (rotate.hip): out = (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)) under the rotation key of
 // the Galois element g; ct, out [K][2][Ll][N], not overlapping; scratch = ks_scratch_bytes(.., K).
 void launch_rotate(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,

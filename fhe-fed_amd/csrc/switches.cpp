@@ -58,6 +58,8 @@ void reload_switches() {
     if (atoll(e) > 0) s.dot_slice_cts = (uint64_t)atoll(e);
   if (const char* e = getenv("SHELFI_GRAM_SLICE_CTS"))
     if (atoll(e) > 0) s.gram_slice_cts = (uint64_t)atoll(e);
+  if (const char* e = getenv("SHELFI_DOTP_SLICE_CTS"))
+    if (atoll(e) > 0) s.dotp_slice_cts = (uint64_t)atoll(e);
   if (const char* e = getenv("SHELFI_WAVG_CHUNK_MIB"))
     if (atoll(e) > 0) s.wavg_chunk_mib = (uint64_t)atoll(e);
   if (const char* e = getenv("SHELFI_STAGE_SLOT_MIB"))

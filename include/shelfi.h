@@ -429,6 +429,28 @@ size_t shelfi_gram_pairs(size_t C);
 /* slices S of the last successful shelfi_dev_gram on this context (a refused call leaves it unchanged; for
  * tests of the split) */
 uint64_t shelfi_gram_slice_count(const shelfi_ctx* ctx);
+/* cc->EvalInnerProduct(ct, pt) (EvalMult(ct, pt) + EvalAddMany) for every pair of C ciphertext batches and R
+ * plaintext batches, as one call: out_dev [C R][2][towers][N], entry c R + r, holds per tower, coefficient and
+ * component i the canonical sum_k u_{c,k,i} p_{r,k} mod q_t -- the projection of learner c's update on the known
+ * vector r (cosine screening against a server update, centred clipping, sketches on public random vectors, and
+ * with one-hot plaintexts the packing of many one-number ciphertexts into one).  batches_dev: a HOST array of C
+ * device pointers [K][2][towers][N], all at one level (the same batch may appear twice); pts_dev [R][K][towers][N]:
+ * R plaintext batches in the layout of shelfi_dev_encode, EVALUATION form, canonical.  Two components, no key of any
+ * kind; level and depth are the ciphertexts', scale = scale_ct scale_pt; at C = R = K = 1 the result is
+ * shelfi_dev_mult_plain's bit for bit.  C or R outside 1..32, K = 0, towers outside 1..L, a NULL pointer (the array,
+ * an entry, pts_dev, out_dev) and out_dev overlapping any input: SHELFI_ERR_ARG; a refused call writes nothing.  A
+ * workgroup serves a tile of 2 x 2 (learners x plaintexts), so a learner's batch is read ceil(R / 2) times and a
+ * plaintext batch ceil(C / 2) times; at R = 1 the learners go four, then two, then one to a tile (C / 4 + at most 2
+ * tiles, the plaintext batch read once for each).  The K ciphertexts are summed
+ * in S = min(16, ceil(K / SHELFI_DOTP_SLICE_CTS), ceil(1024 / G)) slices, G = tiles x towers x max(1, N / 512)
+ * workgroups a slice, lowered until the partial sums (S C R ciphertexts) fit SHELFI_EVAL_CHUNK_MIB; no output bit
+ * depends on the tiles or on S.  With S = 1 the call takes no scratch and returns with the work enqueued on
+ * `stream`; with S > 1 it uses the context's scratch and synchronises `stream` before returning. */
+int shelfi_dev_project(shelfi_ctx* ctx, const uint64_t* const* batches_dev, size_t C, const uint64_t* pts_dev,
+                       size_t R, size_t K, uint32_t towers, uint64_t* out_dev, void* stream);
+/* slices S of the last successful shelfi_dev_project (cc->EvalInnerProduct(ct, pt)) on this context (a refused call
+ * leaves it unchanged; for tests of the split) */
+uint64_t shelfi_dotp_slice_count(const shelfi_ctx* ctx);
 /* cc->ModReduce / Rescale: [K][2][towers][N] -> [K][2][towers-1][N] (no overlap), dividing by
  * q_{towers-1} with rounding; scale / q_{towers-1}. */
 int shelfi_dev_rescale(shelfi_ctx* ctx, const uint64_t* in_dev, size_t K, uint32_t towers, uint64_t* out_dev,
