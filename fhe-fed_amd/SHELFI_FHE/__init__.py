@@ -37,7 +37,7 @@ def reload_switches() -> None:
     library reads them when a context is created and here, never on a launch path."""
     _lib.load().shelfi_reload_switches()
 
-_WIRE_CODES = {"shelfi": 0, "palisade": 1, "packed": 2}  # shelfi_set_wire_format's numbering
+_WIRE_CODES = {"shelfi": 0, "palisade": 1, "packed": 2, "seeded": 3}  # shelfi_set_wire_format's numbering
 
 
 _PyBytes_FromStringAndSize = C.pythonapi.PyBytes_FromStringAndSize
@@ -100,7 +100,7 @@ class CKKS(Scheme):
         if scheme.lower() != "ckks":
             raise ValueError("only the 'ckks' scheme is implemented")
         if wireFormat not in _WIRE_CODES:
-            raise ValueError("wireFormat must be 'palisade', 'shelfi' or 'packed'")
+            raise ValueError("wireFormat must be 'palisade', 'shelfi', 'packed' or 'seeded'")
         self._wire = wireFormat
         self.batchSize = int(batchSize)
         self.scaleFactorBits = int(scaleFactorBits)
@@ -150,14 +150,19 @@ class CKKS(Scheme):
         archive of vector<Ciphertext<DCRTPoly>> (ckks.cpp:98-100; the default, in effect
         once keys are generated or loaded in PALISADE's files), "shelfi" = this library's
         blob, "packed" = this library's blob with the residues at their moduli's bit widths
-        (version 2; 15% fewer bytes at 2^15/L4 over the network and PCIe).  The choice
+        (version 2; 15% fewer bytes at 2^15/L4 over the network and PCIe), "seeded" = for learners
+        that hold the secret key, as the reference's do: encrypt is symmetric and only c0 travels,
+        packed, with the 32-byte public seed c1 is expanded from on the device (version 3; half of
+        "packed"'s bytes; DESIGN.md §2.17.  It needs the whole secret key, not a threshold share, and
+        has no large-value path: a coefficient above 2^61 is a ValueError).  The choice
         sticks across later loadCryptoParams / genCryptoContextAndKeyGen / set_keys calls
         ("palisade" needs keys from PALISADE files or genCryptoContextAndKeyGen; after
         set_keys it answers in "shelfi").
-        computeWeightedAverage and decrypt accept all three and computeWeightedAverage
-        answers in its inputs' format."""
+        computeWeightedAverage and decrypt accept all four and computeWeightedAverage
+        answers in its inputs' format (seeded inputs: in "packed", a sum of seeded ciphertexts
+        is not seeded)."""
         if fmt not in _WIRE_CODES:
-            raise ValueError("wire format must be 'palisade', 'shelfi' or 'packed'")
+            raise ValueError("wire format must be 'palisade', 'shelfi', 'packed' or 'seeded'")
         check(self._lib.shelfi_set_wire_format(self._ctx, _WIRE_CODES[fmt]), "set_wire_format")
         self._wire = fmt
 
@@ -601,9 +606,11 @@ def blob_info(blob: bytes) -> dict:
     kid = C.c_uint64()
     check(lib.shelfi_blob_info(C.cast(C.c_char_p(blob), _lib.u8p), len(blob), C.byref(k),
                                C.byref(d), C.byref(s), C.byref(kid)), "blob_info")
+    ver = C.c_uint32()
+    check(lib.shelfi_blob_version(C.cast(C.c_char_p(blob), _lib.u8p), len(blob), C.byref(ver)), "blob_info")
     return {"num_cts": int(k.value), "depth": int(d.value), "scale": float(s.value),
             "key_id": int(kid.value),
-            "format": "packed" if int.from_bytes(bytes(blob[4:6]), "little") == 2 else "shelfi"}
+            "format": {2: "packed", 3: "seeded"}.get(int(ver.value), "shelfi")}
 
 
 def partial_blob_info(blob: bytes) -> dict:
@@ -663,6 +670,8 @@ def blob_residues(blob: bytes, ring_dim: int, num_towers: int, ckks: "CKKS | Non
     lib = _lib.load()
     hdr = lib.shelfi_blob_header_bytes()
     version = int.from_bytes(bytes(blob[4:6]), "little")
+    if version == 3:
+        raise ValueError("a seeded blob's c1 is expanded on the device: use device.from_blob(ckks, blob)")
     if version == 2:
         if ckks is None:
             raise ValueError("a packed blob needs its context to unpack (blob_residues(..., ckks=ck))")

@@ -124,6 +124,11 @@ SIGNATURES = {
                                    C.POINTER(u8p), C.POINTER(C.c_size_t)]),
     "shelfi_blob_header_bytes": (C.c_size_t, []),
     "shelfi_blob_unpack": (C.c_int, [C.c_void_p, u8p, C.c_size_t, u64p]),
+    "shelfi_blob_version": (C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "shelfi_dev_encrypt_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "shelfi_dev_expand_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint64,
+                                           C.c_void_p]),
+    "shelfi_dev_blob_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "shelfi_dev_wavg": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), f32p, C.c_size_t, C.c_size_t,
                                   C.c_void_p, C.c_void_p]),
     "shelfi_arena_words": (C.c_size_t, [C.c_void_p, C.c_size_t, C.c_size_t]),

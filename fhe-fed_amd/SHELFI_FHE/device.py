@@ -837,6 +837,70 @@ def ntt(ckks, polys, inverse: bool = False):
     return polys
 
 
+def encrypt_seeded(ckks, x):
+    """The symmetric encrypt of a float64 CUDA vector into K = ceil(n / batch) seeded ciphertexts
+    (DESIGN.md §2.17): (c0, seed) with c0 an int64 tensor [K][L][N] and seed the call's 32 public bytes;
+    expand_seeded(ckks, c0, seed) is the ordinary batch.  Needs the whole secret key (not a threshold
+    share); a coefficient above 2^61 in magnitude, or a non-finite value, raises ValueError."""
+    torch = _torch()
+    if not x.is_cuda or x.dtype != torch.float64:
+        raise ValueError("x must be a float64 CUDA tensor")
+    x = x.contiguous().view(-1)
+    inf = ckks.info()
+    K = (x.numel() + inf["batch"] - 1) // inf["batch"]
+    c0 = torch.empty((K, inf["num_towers"], inf["ring_dim"]), dtype=torch.int64, device=x.device)
+    seed = (C.c_uint8 * 32)()
+    check(_lib.load().shelfi_dev_encrypt_seeded(ckks._ctx, C.c_void_p(x.data_ptr()), x.numel(),
+                                                C.c_void_p(c0.data_ptr()), seed, C.c_void_p(_stream_ptr(x))),
+          "dev_encrypt_seeded")
+    return c0, bytes(seed)
+
+
+def expand_seeded(ckks, c0, seed: bytes, k0: int = 0, out=None):
+    """c0 [K][l][N] (l <= L towers) and a 32-byte seed -> the batch [K][2][l][N]: polynomial 0 is c0,
+    polynomial 1 the seed's stream of ciphertexts k0 .. k0 + K - 1 (k0: the first one's index in its
+    blob).  An ordinary batch for Arena.put, wavg, decrypt and the rest."""
+    torch = _torch()
+    L, N = _ln(ckks)
+    if (not c0.is_cuda or not c0.is_contiguous() or c0.dtype != torch.int64 or c0.dim() != 3 or c0.shape[2] != N
+            or not 1 <= c0.shape[1] <= L):
+        raise ValueError("c0 must be a contiguous int64 CUDA tensor [K][l][N] with l <= L")
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("the seed is 32 bytes")
+    if not 0 <= int(k0) < 1 << 48:
+        raise ValueError("ciphertext index at or above 2^48")
+    K, l = int(c0.shape[0]), int(c0.shape[1])
+    if out is None:
+        out = torch.empty((K, 2, l, N), dtype=torch.int64, device=c0.device)
+    if (not out.is_cuda or not out.is_contiguous() or out.dtype != torch.int64 or tuple(out.shape) != (K, 2, l, N)
+            or out.device != c0.device):
+        raise ValueError("out must be a contiguous int64 [K][2][l][N] tensor on c0's device")
+    out[:, 0].copy_(c0)
+    check(_lib.load().shelfi_dev_expand_seeded(ckks._ctx, C.c_void_p(out.data_ptr()), K, l,
+                                               (C.c_uint8 * 32).from_buffer_copy(seed), int(k0),
+                                               C.c_void_p(_stream_ptr(out))), "dev_expand_seeded")
+    return out
+
+
+def from_blob(ckks, blob, out=None):
+    """Ciphertext bytes in any wire format -> the [K][2][L][N] batch on the device: a packed blob is
+    unpacked and a seeded blob's c1 expanded there (the host cannot: blob_residues refuses one)."""
+    import numpy as np
+
+    from . import blob_info
+
+    K = blob_info(bytes(blob))["num_cts"]
+    if out is None:
+        out = empty_ct(ckks, K)
+    _check_ct(out, ckks, K)
+    host = np.frombuffer(blob, dtype=np.uint8)
+    check(_lib.load().shelfi_dev_blob_unpack(ckks._ctx, C.c_void_p(host.ctypes.data), host.size, K,
+                                             C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(out))),
+          "dev_blob_unpack")
+    return out
+
+
 def from_bytes(ckks, blob: bytes, device=None):
     """Blob payload -> device ciphertext tensor (one H2D copy)."""
     import numpy as np

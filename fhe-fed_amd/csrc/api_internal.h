@@ -63,6 +63,10 @@ void stream_key(const shelfi_ctx* ctx, uint32_t key[8]);
 // encryption stream key + first ciphertext index for this call
 void draw_key(shelfi_ctx* ctx, uint64_t count, uint32_t key[8], uint64_t* g0);
 
+// the public seed of a seeded encrypt call: the first eight words of the block (counter 0, nonce
+// (9 << 56) | g0) of the call's stream key -- a block no other draw reads
+void seeded_seed(const uint32_t key[8], uint64_t g0, uint32_t seed[8]);
+
 // Zeroes a call's stream key when the call leaves its scope, by return or by exception.
 struct KeyWiper {
   uint32_t* key;
@@ -91,6 +95,8 @@ struct BlobHeader {
   uint32_t encoding;       // 4 = CKKSPacked (PALISADE PlaintextEncodings)
 };
 static_assert(sizeof(BlobHeader) == 64, "blob header must be 64 bytes");
+// A seeded blob (version 3): the header, the 32-byte public seed, 32 zero bytes, then the payload
+constexpr size_t kSeededLeadBytes = 128;
 // A partial decryption (threshold scheme) travels under the same 64-byte header with magic "SHPD",
 // version 1 and a payload of K x L x N uint64 residues [ct][tower][coeff]: logN, L, K, depth, scale,
 // params_id, batch and encoding as in the ciphertexts it was made from, key_id the joint public key's.
@@ -111,7 +117,9 @@ struct CtLayout {
   uint8_t* base = nullptr;
   bool pal = false;
   bool packed = false;  // a version-2 (packed) library blob
-  int fmt() const { return pal ? 1 : packed ? 2 : 0; }  // shelfi_set_wire_format's numbering
+  bool seeded = false;  // a version-3 (seeded) library blob: c0 groups only, c1 expanded from `seed`
+  uint32_t seed[8] = {};
+  int fmt() const { return pal ? 1 : packed ? 2 : seeded ? 3 : 0; }  // shelfi_set_wire_format's numbering
   uint64_t K = 0;
   uint32_t depth = 0;
   uint64_t level = 0;
@@ -123,15 +131,16 @@ struct CtLayout {
     out.clear();
     if (!Lu) Lu = p.L;
     const size_t poly_bytes = (size_t)p.L * p.N * 8, ct_bytes = 2 * poly_bytes;
-    if (packed) {  // (ct, poly) groups of packed rows; a tower prefix is a prefix of each group
+    if (packed || seeded) {  // (ct, poly) groups of packed rows; a tower prefix is a prefix of each group
       const uint64_t pg = packed_poly_bytes(p, p.L);
+      const uint64_t gpc = seeded ? 1 : 2;  // groups per ciphertext: a seeded one carries its c0 alone
+      uint8_t* const pay = base + (seeded ? kSeededLeadBytes : sizeof(BlobHeader));
       if (Lu == p.L) {
-        out.push_back(HostPiece{base + sizeof(BlobHeader) + k0 * 2 * pg, kn * 2 * pg});
+        out.push_back(HostPiece{pay + k0 * gpc * pg, kn * gpc * pg});
         return;
       }
       const uint64_t pl = packed_poly_bytes(p, Lu);
-      for (uint64_t i = 2 * k0; i < 2 * (k0 + kn); ++i)
-        out.push_back(HostPiece{base + sizeof(BlobHeader) + i * pg, (size_t)pl});
+      for (uint64_t i = gpc * k0; i < gpc * (k0 + kn); ++i) out.push_back(HostPiece{pay + i * pg, (size_t)pl});
       return;
     }
     if (!pal) {
@@ -151,8 +160,14 @@ struct CtLayout {
 // A caller's ciphertext batch, validated against the context (params and key).
 CtLayout open_cts(const shelfi_ctx* ctx, const uint8_t* b, size_t len);
 // Size of (and, with buf, the header / framing of) an output batch in format fmt; returns its layout.
+// (seed: the public seed a seeded batch's framing carries)
 CtLayout make_output(const shelfi_ctx* ctx, int fmt, uint64_t K, uint32_t depth, uint64_t level, double scale,
-                     uint8_t* buf, size_t* total);
+                     uint8_t* buf, size_t* total, const uint32_t* seed = nullptr);
+// What a batch lands as on the device: a seeded blob's c0 groups (ciphertexts k0 .. of the blob, each
+// polynomial's first Lu towers, packed at src) into a [kn][2][Lu][N] batch at dst with c1 expanded beside
+// them; ap = arena_pack_prefix(p, Lu).  On the stream s (the compute stream of a pipeline).
+void seeded_land(const shelfi_ctx* ctx, const CtLayout& v, const uint8_t* src, uint64_t k0, uint64_t kn, uint32_t Lu,
+                 const ArenaPack& ap, uint64_t* dst, hipStream_t s);
 
 // -------------------------------------------------------- bytes_api.cpp ----
 // The ctx's pinned staging rings, created on first use

@@ -70,13 +70,16 @@ static void encrypt_bytes_pipeline(shelfi_ctx* ctx, const double* x, size_t n, u
   kc = std::min<uint64_t>(kc, K);
   const size_t xin = kc * p.batch * 8, cto = kc * ct_bytes;
   // packed wire output: the chunk is packed on the device (U_t bits per residue) before its D2H
-  const size_t pko = dst.packed ? kc * 2 * packed_poly_bytes(p, p.L) : 0;
+  // seeded wire output: the symmetric encrypt's c0 [kc][L][N] takes the chunk's uint64 buffer and is packed
+  // one group a ciphertext
+  const size_t pko = dst.packed ? kc * 2 * packed_poly_bytes(p, p.L) : dst.seeded ? kc * packed_poly_bytes(p, p.L) : 0;
   uint8_t* io = (uint8_t*)ensure(ctx->io, ctx->io_bytes, 2 * (xin + cto + pko));
   uint8_t* xb[2] = {io, io + xin};
   uint8_t* cb[2] = {io + 2 * xin, io + 2 * xin + cto};
   uint8_t* pb[2] = {io + 2 * (xin + cto), io + 2 * (xin + cto) + pko};
   const ArenaPack ap = arena_pack(p);
-  void* scratch = ensure(ctx->scratch, ctx->scratch_bytes, encrypt_scratch_bytes(p, kc));
+  void* scratch = ensure(ctx->scratch, ctx->scratch_bytes,
+                         dst.seeded ? seeded_encrypt_scratch_bytes(p, kc) : encrypt_scratch_bytes(p, kc));
   Pipe pp(ctx);
   StageRun sr(stager(ctx));
   std::vector<HostPiece> pcs;
@@ -91,7 +94,10 @@ static void encrypt_bytes_pipeline(shelfi_ctx* ctx, const double* x, size_t n, u
     SHELFI_HIP(hipEventRecord(pp.in_ready[b], pp.a));
     SHELFI_HIP(hipStreamWaitEvent(pp.b, pp.in_ready[b], 0));
     if (ci >= 2) SHELFI_HIP(hipStreamWaitEvent(pp.b, pp.out_free[b], 0));  // ct buffer drained
-    if (approx)
+    if (dst.seeded)
+      launch_encrypt_seeded(p, ctx->dt, ctx->dk, (const double*)xb[b], xn, kn, (uint64_t*)cb[b], scratch, key,
+                            g0 + k0, dst.seed, k0, fl, pp.b);
+    else if (approx)
       launch_encrypt_approx(p, ctx->dt, ctx->dk, (const double*)xb[b], xn, kn, (uint64_t*)cb[b], scratch, key,
                             g0 + k0, pp.b);
     else
@@ -100,15 +106,24 @@ static void encrypt_bytes_pipeline(shelfi_ctx* ctx, const double* x, size_t n, u
     if (dst.packed)  // canonical residues: the residue check cannot fire
       launch_blob_pack((const uint64_t*)cb[b], kn, p.L, p.logN, ap, ctx->dt.tc, (uint32_t*)pb[b],
                        ctx->dev_flag + 5, pp.b);
+    if (dst.seeded)  // kn groups of L towers: the rows of kn polynomials
+      launch_arena_pack((const uint64_t*)cb[b], 0, kn * p.L << (p.logN - 9), 1, 0, p.L, p.logN, ap, ctx->dt.tc,
+                        (uint64_t*)pb[b], ctx->dev_flag + 5, pp.b);
     SHELFI_HIP(hipEventRecord(pp.computed[b], pp.b));
     SHELFI_HIP(hipStreamWaitEvent(pp.c, pp.computed[b], 0));
     dst.pieces(k0, kn, p, pcs);
-    sr.s.d2hv(pcs.data(), pcs.size(), dst.packed ? pb[b] : cb[b], pp.c);
+    sr.s.d2hv(pcs.data(), pcs.size(), dst.packed || dst.seeded ? pb[b] : cb[b], pp.c);
     SHELFI_HIP(hipEventRecord(pp.out_free[b], pp.c));
     sr.s.poll();
   }
   sr.finish();
   pp.sync();
+  if (dst.seeded) {  // the symmetric encrypt has no large-value path
+    if (gen_flag_raised(ctx, fl, 1)) throw Error{SHELFI_ERR_RANGE, "encrypt (seeded): non-finite input value"};
+    if (gen_flag_raised(ctx, fl, 0))
+      throw Error{SHELFI_ERR_RANGE, "encrypt (seeded): a coefficient |x * scale| above 2^61 (the symmetric encrypt has no large-value path)"};
+    return;
+  }
   if (!approx && encode_needs_approx(ctx, fl)) {  // once per call, whichever chunks were flagged
     ++ctx->encode_redo_count;
     encrypt_bytes_pipeline(ctx, x, n, K, dst, key, g0, true);
@@ -127,6 +142,8 @@ static std::vector<CtLayout> wavg_inputs(const shelfi_ctx* ctx, const uint8_t* c
     const CtLayout& h0 = in.front();
     if (h.pal != h0.pal)
       throw Error{SHELFI_ERR_FORMAT, "learners mix PALISADE archives and library blobs"};
+    if (h.seeded != h0.seeded)
+      throw Error{SHELFI_ERR_FORMAT, "learners mix seeded and other library blobs"};
     if (h.packed != h0.packed)
       throw Error{SHELFI_ERR_FORMAT, "learners mix packed and uint64 library blobs"};
     if (h.K != h0.K)
@@ -173,12 +190,15 @@ static void wavg_bytes_pipeline(shelfi_ctx* ctx, const std::vector<CtLayout>& in
   if (!direct && !switches().wavg_chunk_mib) kc = std::min<uint64_t>(kc, std::max<uint64_t>(1, (K + 3) / 4));
   // packed wire (version-2 blobs): uploads land packed and are unpacked on the device; a packed
   // output is packed before its D2H
-  const uint64_t pct = 2 * packed_poly_bytes(p, p.L);
-  const bool pin = in.front().packed, pout = dst.packed;
+  // seeded inputs (version-3 blobs): each ciphertext's c0 lands as one packed group; it is unpacked into
+  // polynomial 0 and c1 expanded beside it, both on the compute stream
+  const bool sin = in.front().seeded;
+  const uint64_t pct = 2 * packed_poly_bytes(p, p.L), pct_in = sin ? pct / 2 : pct;
+  const bool pin = in.front().packed || sin, pout = dst.packed;
   const bool raw = in.front().pal;  // archives: raw ranges, gathered on the device
   kc = std::min<uint64_t>(kc, K);
   const size_t in_chunk = group * kc * ct_bytes, out_chunk = kc * ct_bytes;
-  const size_t pin_chunk = pin ? group * kc * pct : 0, pout_chunk = pout ? kc * pct : 0;
+  const size_t pin_chunk = pin ? group * kc * pct_in : 0, pout_chunk = pout ? kc * pct : 0;
   const uint64_t nchunks = (K + kc - 1) / kc;
   std::vector<HostPiece> pcs;
   // raw ranges: a step's (chunk, learner group) learners' byte ranges (tower headers included) land back to
@@ -314,7 +334,7 @@ static void wavg_bytes_pipeline(shelfi_ctx* ctx, const std::vector<CtLayout>& in
         const uint8_t* lo = pcs.front().p;
         const size_t span = (size_t)(pcs.back().p + pcs.back().n - lo);
         if (direct) {  // one pageable copy of the learner's whole range
-          uint8_t* land = land0 + (raw ? off : c * kn * (pin ? pct : ct_bytes));
+          uint8_t* land = land0 + (raw ? off : c * kn * (pin ? pct_in : ct_bytes));
           const auto t0 = clk::now();
           if (two && (c & 1))  // every other learner from the second thread: two copies in flight
             ctx->up2->post(land, lo, span, ctx->stream4);
@@ -344,9 +364,13 @@ static void wavg_bytes_pipeline(shelfi_ctx* ctx, const std::vector<CtLayout>& in
         launch_gather_runs(rawb[bi], tabd + step_run0[st], step_run0[st + 1] - step_run0[st], (uint32_t)(p.N * 8),
                            inb[bi], pp.b);
       if (pin)  // unpacked on the compute stream, so the upload stream moves on to the next chunk
-        for (size_t c = 0; c < gc; ++c)
-          launch_blob_unpack((const uint32_t*)(pinb[bi] + c * kn * pct), kn, p.L, p.logN, ap,
-                             (uint64_t*)(inb[bi] + c * kn * ct_bytes), pp.b);
+        for (size_t c = 0; c < gc; ++c) {
+          uint64_t* const ub = (uint64_t*)(inb[bi] + c * kn * ct_bytes);
+          if (sin)
+            seeded_land(ctx, in[c0 + c], pinb[bi] + c * kn * pct_in, k0, kn, p.L, ap, ub, pp.b);
+          else
+            launch_blob_unpack((const uint32_t*)(pinb[bi] + c * kn * pct), kn, p.L, p.logN, ap, ub, pp.b);
+        }
       if (ci >= 2 && c0 == 0) SHELFI_HIP(hipStreamWaitEvent(pp.b, pp.out_free[b], 0));
       WavgArgs a;
       std::memset(&a, 0, sizeof(a));
@@ -431,6 +455,7 @@ int shelfi_encrypt_into(shelfi_ctx* ctx, const double* x, size_t n, uint8_t* out
   std::lock_guard<std::mutex> lk(ctx->mu);
   return guarded([&] {
     require_keys(ctx);
+    if (ctx->wire == 3) require_own_secret(ctx);
     DeviceGuard g(ctx->device);
     const Params& p = ctx->p;
     const uint64_t K = (n + p.batch - 1) / p.batch;  // ckks.cpp:65
@@ -443,14 +468,15 @@ int shelfi_encrypt_into(shelfi_ctx* ctx, const double* x, size_t n, uint8_t* out
     // residues first (the parallel drains first-touch the fresh pages), framing after
     CtLayout dst = make_output(ctx, ctx->wire, K, 1, 0, p.delta, nullptr, &total);
     dst.base = out;
-    if (K) {
+    if (K || dst.seeded) {
       uint32_t key[8];
       KeyWiper wipe(key);
       uint64_t g0;
       draw_key(ctx, K, key, &g0);
-      encrypt_bytes_pipeline(ctx, x, n, K, dst, key, g0, false);
+      if (dst.seeded) seeded_seed(key, g0, dst.seed);  // an empty batch carries a seed too
+      if (K) encrypt_bytes_pipeline(ctx, x, n, K, dst, key, g0, false);
     }
-    make_output(ctx, ctx->wire, K, 1, 0, p.delta, out, &total);
+    make_output(ctx, ctx->wire, K, 1, 0, p.delta, out, &total, dst.seed);
   });
 }
 
@@ -472,7 +498,7 @@ int shelfi_weighted_average_into(shelfi_ctx* ctx, const uint8_t* const* blobs, c
       // ckks.cpp:270-309: with no learners the loop never runs and the empty
       // vector<Ciphertext> is serialized; here an empty batch in the ctx's wire format
       // (depth 2 / scale Delta^2: what a weighted average of fresh ciphertexts carries)
-      const int fmt = ctx->wire;
+      const int fmt = ctx->wire == 3 ? 2 : ctx->wire;  // an aggregate is never seeded
       const double scale = ctx->p.delta * ctx->p.delta;
       size_t total = 0;
       make_output(ctx, fmt, 0, 2, 0, scale, nullptr, &total);
@@ -489,22 +515,24 @@ int shelfi_weighted_average_into(shelfi_ctx* ctx, const uint8_t* const* blobs, c
     const std::vector<CtLayout> in = wavg_inputs(ctx, blobs, lens, C);
     const auto t_parsed = clk::now();
     const CtLayout& h0 = in.front();
+    // a sum of seeded ciphertexts is not seeded: the answer to seeded inputs is packed
+    const int ofmt = h0.seeded ? 2 : h0.fmt();
     // EvalMult by a constant (ckks.cpp:288): depth + 1, scale * Delta, same level
     const uint32_t depth = h0.depth + 1;
     const double scale = h0.scale * ctx->p.delta;
     size_t total = 0;
-    make_output(ctx, h0.fmt(), h0.K, depth, h0.level, scale, nullptr, &total);
+    make_output(ctx, ofmt, h0.K, depth, h0.level, scale, nullptr, &total);
     *out_len = total;
     if (!out) return;  // size query
     if (out_cap < total) throw Error{SHELFI_ERR_ARG, "output buffer too small"};
     advise_huge(out, total);
     // residues first (the parallel drains first-touch the fresh pages), framing after
-    CtLayout dst = make_output(ctx, h0.fmt(), h0.K, depth, h0.level, scale, nullptr, &total);
+    CtLayout dst = make_output(ctx, ofmt, h0.K, depth, h0.level, scale, nullptr, &total);
     dst.base = out;
     const auto t_pipe = clk::now();
     if (h0.K) wavg_bytes_pipeline(ctx, in, weights, C, h0.K, dst, lens);
     const auto t_done = clk::now();
-    make_output(ctx, h0.fmt(), h0.K, depth, h0.level, scale, out, &total);
+    make_output(ctx, ofmt, h0.K, depth, h0.level, scale, out, &total);
     if (switches().stage_trace) {
       const auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count() * 1e3; };
       std::fprintf(stderr, "[wavg-call] parse %.3f ms, setup %.3f, pipeline %.3f, framing %.3f, total %.3f\n",
@@ -552,8 +580,10 @@ int shelfi_decrypt(shelfi_ctx* ctx, const uint8_t* blob, size_t len, size_t n, d
       kc = std::min<uint64_t>(kc, K);
       const size_t cin = kc * ct_bytes, dout = kc * p.batch * 8;
       // a packed blob's tower prefix lands packed and is unpacked on the device
-      const uint64_t ppre = 2 * packed_poly_bytes(p, pd.L);  // packed bytes of one ciphertext's prefix
-      const size_t pin = h.packed ? kc * ppre : 0;
+      // (a seeded blob's c0 prefix lands the same way, and c1's prefix is expanded beside it)
+      const bool hp = h.packed || h.seeded;
+      const uint64_t ppre = (h.seeded ? 1 : 2) * packed_poly_bytes(p, pd.L);  // packed bytes of one ciphertext's prefix
+      const size_t pin = hp ? kc * ppre : 0;
       uint8_t* io = (uint8_t*)ensure(ctx->io, ctx->io_bytes, 2 * (cin + dout + pin));
       uint8_t* cb[2] = {io, io + cin};
       uint8_t* ob[2] = {io + 2 * cin, io + 2 * cin + dout};
@@ -572,10 +602,11 @@ int shelfi_decrypt(shelfi_ctx* ctx, const uint8_t* blob, size_t len, size_t n, d
         const uint64_t o0 = k0 * p.batch, on = std::min<uint64_t>(n - o0, kn * p.batch);
         if (ci >= 2) SHELFI_HIP(hipStreamWaitEvent(pp.a, pp.computed[b], 0));
         h.pieces(k0, kn, p, pcs, pd.L);
-        sr.s.h2dv(h.packed ? pb[b] : cb[b], pcs.data(), pcs.size(), pp.a);
+        sr.s.h2dv(hp ? pb[b] : cb[b], pcs.data(), pcs.size(), pp.a);
         SHELFI_HIP(hipEventRecord(pp.in_ready[b], pp.a));
         SHELFI_HIP(hipStreamWaitEvent(pp.b, pp.in_ready[b], 0));
         if (h.packed) launch_blob_unpack((const uint32_t*)pb[b], kn, pd.L, p.logN, apd, (uint64_t*)cb[b], pp.b);
+        if (h.seeded) seeded_land(ctx, h, pb[b], k0, kn, pd.L, apd, (uint64_t*)cb[b], pp.b);
         if (ci >= 2) SHELFI_HIP(hipStreamWaitEvent(pp.b, pp.out_free[b], 0));
         dn.g0 += (ci ? kc : 0);
         launch_decrypt(pd, dtd, ctx->dk, (const uint64_t*)cb[b], kn, h.scale, on, (double*)ob[b],
@@ -620,8 +651,9 @@ int shelfi_partial_decrypt(shelfi_ctx* ctx, const uint8_t* blob, size_t len, int
     std::memcpy(res.p, &hd, sizeof(hd));
     if (h.K) {
       const uint64_t kc = std::min<uint64_t>(h.K, std::max<uint64_t>(1, (64ull << 20) / (2 * poly_bytes)));
-      const uint64_t pct = 2 * packed_poly_bytes(p, p.L);
-      const size_t cin = kc * 2 * poly_bytes, pout = kc * poly_bytes, pin = h.packed ? kc * pct : 0;
+      const bool hp = h.packed || h.seeded;
+      const uint64_t pct = (h.seeded ? 1 : 2) * packed_poly_bytes(p, p.L);
+      const size_t cin = kc * 2 * poly_bytes, pout = kc * poly_bytes, pin = hp ? kc * pct : 0;
       uint8_t* io = (uint8_t*)ensure(ctx->io, ctx->io_bytes, cin + pout + pin);
       uint8_t *cb = io, *ob = io + cin, *pb = io + cin + pout;
       const ArenaPack ap = arena_pack(p);
@@ -631,8 +663,9 @@ int shelfi_partial_decrypt(shelfi_ctx* ctx, const uint8_t* blob, size_t len, int
       for (uint64_t k0 = 0; k0 < h.K; k0 += kc) {
         const uint64_t kn = std::min<uint64_t>(kc, h.K - k0);
         h.pieces(k0, kn, p, pcs);
-        sr.s.h2dv(h.packed ? pb : cb, pcs.data(), pcs.size(), s);
+        sr.s.h2dv(hp ? pb : cb, pcs.data(), pcs.size(), s);
         if (h.packed) launch_blob_unpack((const uint32_t*)pb, kn, p.L, p.logN, ap, (uint64_t*)cb, s);
+        if (h.seeded) seeded_land(ctx, h, pb, k0, kn, p.L, ap, (uint64_t*)cb, s);
         partial_decrypt_locked(ctx, (const uint64_t*)cb, kn, p.L, lead != 0, (uint64_t*)ob, s);
         SHELFI_HIP(hipMemcpy(res.p + sizeof(BlobHeader) + k0 * poly_bytes, ob, kn * poly_bytes,
                              hipMemcpyDeviceToHost));

@@ -40,6 +40,42 @@ void fill_weights(WavgArgs& a, const Params& p, const float* w, size_t n) {
   for (size_t c = 0; c < n; ++c) weight_limbs(w[c], p, &a.wl[c][0][0]);
 }
 
+// RFC 8439's block function as the kernels run it (dev_common.h chacha20_block: a 64-bit counter in words
+// 12-13, a 64-bit nonce in words 14-15), for the one block a seeded encrypt call derives its seed from.
+static void chacha20_block_host(const uint32_t key[8], uint64_t counter, uint64_t nonce, uint32_t out[16]) {
+  const uint32_t s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key[0], key[1], key[2], key[3],
+                          key[4], key[5], key[6], key[7], (uint32_t)counter, (uint32_t)(counter >> 32),
+                          (uint32_t)nonce, (uint32_t)(nonce >> 32)};
+  uint32_t x[16];
+  std::memcpy(x, s, sizeof(x));
+  const auto rotl = [](uint32_t v, int n) { return (v << n) | (v >> (32 - n)); };
+  const auto qr = [&](int a, int b, int c, int d) {
+    x[a] += x[b]; x[d] = rotl(x[d] ^ x[a], 16);
+    x[c] += x[d]; x[b] = rotl(x[b] ^ x[c], 12);
+    x[a] += x[b]; x[d] = rotl(x[d] ^ x[a], 8);
+    x[c] += x[d]; x[b] = rotl(x[b] ^ x[c], 7);
+  };
+  for (int i = 0; i < 10; ++i) {
+    qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15);
+    qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14);
+  }
+  for (int i = 0; i < 16; ++i) out[i] = x[i] + s[i];
+}
+
+void seeded_seed(const uint32_t key[8], uint64_t g0, uint32_t seed[8]) {
+  uint32_t blk[16];
+  chacha20_block_host(key, 0, (9ull << 56) | g0, blk);
+  std::memcpy(seed, blk, 32);
+  explicit_bzero(blk, sizeof(blk));
+}
+
+void seeded_land(const shelfi_ctx* ctx, const CtLayout& v, const uint8_t* src, uint64_t k0, uint64_t kn, uint32_t Lu,
+                 const ArenaPack& ap, uint64_t* dst, hipStream_t s) {
+  const Params& p = ctx->p;
+  launch_blob_unpack_groups((const uint32_t*)src, kn, Lu, p.logN, ap, dst, 2ull * Lu * p.N, s);
+  launch_seeded_expand(v.seed, k0, kn, Lu, p.logN, ctx->dt.tc, dst, s);
+}
+
 // A call's generation of the GenFlag words (shelfi_internal.h).  Every caller synchronises before the next
 // call starts, so no kernel writes the words while the host clears them at a wrap of the counter.
 GenFlag next_gen_flag(shelfi_ctx* ctx) {

@@ -455,6 +455,7 @@ static void install_keys(shelfi_ctx* ctx, const uint64_t* pk, const uint64_t* sk
   ctx->sk_host.assign(sk, sk + LN);
   ctx->key_id = fnv1a(pk, sizeof(uint64_t) * 2 * LN, ctx->params_id);
   ctx->keys_loaded = true;
+  ctx->threshold_share = false;  // shelfi_multiparty_keygen raises it again after its install
   ctx->palisade_keys = palisade;
   if (!palisade) {  // PALISADE wire format needs the PALISADE context + key tag
     ctx->pal_ctx_obj.clear();
@@ -467,6 +468,14 @@ void require_keys(const shelfi_ctx* ctx) {
   if (!ctx->keys_loaded)
     throw Error{SHELFI_ERR_STATE,
                 "no keys: call loadCryptoParams() or genCryptoContextAndKeyGen() first"};
+}
+
+// The symmetric (seeded) encrypt: a ciphertext under one party's share of a threshold key is not a
+// ciphertext under the joint key.
+void require_own_secret(const shelfi_ctx* ctx) {
+  require_keys(ctx);
+  if (ctx->threshold_share)
+    throw Error{SHELFI_ERR_STATE, "seeded encryption needs the whole secret key: this context holds a threshold share (multipartyKeyGen)"};
 }
 
 // -------------------------------------------------- own key-file format ----
@@ -777,6 +786,7 @@ int shelfi_multiparty_keygen(shelfi_ctx* ctx, const uint64_t* prev_pk) {
     SHELFI_HIP(hipMemcpyAsync(pk.data(), pk_d.p, 2 * LN * 8, hipMemcpyDeviceToHost, ctx->stream));
     SHELFI_HIP(hipStreamSynchronize(ctx->stream));
     install_keys(ctx, pk.data(), sk.data(), false);
+    ctx->threshold_share = true;
   });
 }
 

@@ -236,6 +236,55 @@ int shelfi_dev_encrypt(shelfi_ctx* ctx, const double* x_dev, size_t n, uint64_t*
   });
 }
 
+// ---- seeded ciphertexts (seeded.hip) ----
+int shelfi_dev_encrypt_seeded(shelfi_ctx* ctx, const double* x_dev, size_t n, uint64_t* c0_dev, uint8_t seed_out[32],
+                              void* stream) {
+  if (!ctx || !seed_out || (n && (!x_dev || !c0_dev))) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    require_own_secret(ctx);
+    DeviceGuard g(ctx->device);
+    const Params& p = ctx->p;
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t K = (n + p.batch - 1) / p.batch;
+    uint32_t key[8], seed[8];
+    KeyWiper wipe(key);
+    uint64_t g0;
+    draw_key(ctx, K, key, &g0);
+    seeded_seed(key, g0, seed);
+    std::memcpy(seed_out, seed, 32);
+    if (!K) return;
+    const GenFlag fl = next_gen_flag(ctx);
+    const size_t c0_words = (size_t)p.L * p.N;
+    const auto bytes_of = [&](uint64_t kc) { return seeded_encrypt_scratch_bytes(p, kc); };
+    for_chunks(ctx, K, switches().dev_chunk_mib, bytes_of, [&](uint64_t k0, uint64_t kc, void* scratch) {
+      const uint64_t xs = k0 * p.batch, xn = std::min<uint64_t>(n - xs, kc * p.batch);
+      launch_encrypt_seeded(p, ctx->dt, ctx->dk, x_dev + xs, xn, kc, c0_dev + k0 * c0_words, scratch, key, g0 + k0,
+                            seed, k0, fl, s);
+    });
+    SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call; the range words are final
+    if (gen_flag_raised(ctx, fl, 1)) throw Error{SHELFI_ERR_RANGE, "encrypt_seeded: non-finite input value"};
+    if (gen_flag_raised(ctx, fl, 0))
+      throw Error{SHELFI_ERR_RANGE, "encrypt_seeded: a coefficient |x * scale| above 2^61 (the symmetric encrypt has no large-value path)"};
+  });
+}
+
+int shelfi_dev_expand_seeded(shelfi_ctx* ctx, uint64_t* ct_dev, size_t K, uint32_t towers, const uint8_t seed[32],
+                             uint64_t k0, void* stream) {
+  if (!ctx || !seed || (K && !ct_dev)) return SHELFI_ERR_ARG;
+  return guarded([&] {
+    const Params& p = ctx->p;
+    require_towers(p, towers);
+    if (k0 >= kSeededMaxCts || K > kSeededMaxCts - k0)
+      throw Error{SHELFI_ERR_ARG, "expand_seeded: ciphertext index at or above 2^48"};
+    if (!K) return;
+    DeviceGuard g(ctx->device);
+    uint32_t sw[8];
+    std::memcpy(sw, seed, 32);  // eight little-endian words
+    launch_seeded_expand(sw, k0, K, towers, p.logN, ctx->dt.tc, ct_dev, (hipStream_t)stream);
+  });
+}
+
 int shelfi_dev_decrypt(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, double scale, size_t n,
                        double* out_dev, void* stream) {
   return dev_decrypt(ctx, ct_dev, K, ctx ? ctx->p.L : 0, scale, n, out_dev, stream);

@@ -238,13 +238,15 @@ int shelfi_dev_arena_put_blob(shelfi_ctx* ctx, const uint8_t* blob, size_t len, 
     std::vector<HostPiece> pcs;
     StageRun sr(stager(ctx));
     // a packed blob lands packed (in the bytes-API buffer, idle under the ctx lock) and is unpacked
-    const uint64_t pct = 2 * packed_poly_bytes(p, p.L);
-    uint8_t* pk = v.packed ? (uint8_t*)ensure(ctx->io, ctx->io_bytes, std::min(K, arena_stage_cts(p)) * pct) : nullptr;
+    // (a seeded blob's c0 groups the same way; c1 is expanded beside them)
+    const bool vp = v.packed || v.seeded;
+    const uint64_t pct = (v.seeded ? 1 : 2) * packed_poly_bytes(p, p.L);
+    uint8_t* pk = vp ? (uint8_t*)ensure(ctx->io, ctx->io_bytes, std::min(K, arena_stage_cts(p)) * pct) : nullptr;
     const ArenaPack ap = arena_pack(p);
     arena_place(ctx, K, learner, C, arena_dev, s, arena_stage_cts(p), true, [&](size_t k0, size_t kn, uint64_t* dst) {
       // a blob: one payload run; an archive: 2 L tower runs per ciphertext
       v.pieces(k0, kn, p, pcs);
-      uint8_t* land = v.packed ? pk : (uint8_t*)dst;
+      uint8_t* land = vp ? pk : (uint8_t*)dst;
       size_t bytes = 0;
       for (const HostPiece& pc : pcs) bytes += pc.n;
       if (arena_use_stager(pcs.size(), bytes)) {
@@ -257,9 +259,52 @@ int shelfi_dev_arena_put_blob(shelfi_ctx* ctx, const uint8_t* blob, size_t len, 
         }
       }
       if (v.packed) launch_blob_unpack((const uint32_t*)pk, kn, p.L, p.logN, ap, dst, s);
+      if (v.seeded) seeded_land(ctx, v, pk, k0, kn, p.L, ap, dst, s);
       return (const uint64_t*)dst;
     });
     sr.finish();
+  });
+}
+
+// Any ciphertext bytes -> the uint64 batch [K][2][L][N] on the device: a uint64 blob or an archive copied, a
+// packed blob unpacked, a seeded blob's c0 unpacked and its c1 expanded (seeded.hip); the header is checked
+// against the context first and the landed residues against their moduli after.
+int shelfi_dev_blob_unpack(shelfi_ctx* ctx, const uint8_t* blob, size_t len, size_t K, uint64_t* out_dev,
+                           void* stream) {
+  if (!ctx || !blob || (K && !out_dev)) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    const CtLayout v = open_cts(ctx, blob, len);
+    if (v.K != K)
+      throw Error{SHELFI_ERR_FORMAT, "blob holds " + std::to_string(v.K) + " ciphertexts, the output " +
+                                         std::to_string(K)};
+    if (!K) return;
+    DeviceGuard g(ctx->device);
+    const Params& p = ctx->p;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t ct_words = 2ull * p.L * p.N, kc = arena_stage_cts(p);
+    const bool vp = v.packed || v.seeded;
+    const uint64_t pct = (v.seeded ? 1 : 2) * packed_poly_bytes(p, p.L);
+    uint8_t* pk = vp ? (uint8_t*)ensure(ctx->io, ctx->io_bytes, std::min(K, kc) * pct) : nullptr;
+    const ArenaPack ap = arena_pack(p);
+    std::vector<HostPiece> pcs;
+    StageRun sr(stager(ctx));
+    for (size_t k0 = 0; k0 < K; k0 += kc) {
+      const size_t kn = std::min(kc, K - k0);
+      uint64_t* dst = out_dev + k0 * ct_words;
+      v.pieces(k0, kn, p, pcs);
+      sr.s.h2dv(vp ? pk : (uint8_t*)dst, pcs.data(), pcs.size(), s);
+      if (v.packed) launch_blob_unpack((const uint32_t*)pk, kn, p.L, p.logN, ap, dst, s);
+      if (v.seeded) seeded_land(ctx, v, pk, k0, kn, p.L, ap, dst, s);
+    }
+    uint32_t* bad = ctx->dev_flag + 6;
+    SHELFI_HIP(hipMemsetAsync(bad, 0, 4, s));
+    launch_check_residues(out_dev, (uint64_t)K * 2 * p.L, p.L, p.logN, ctx->dt.tc, bad, s);
+    SHELFI_HIP(hipMemcpyAsync(ctx->host_flag + 6, bad, 4, hipMemcpyDeviceToHost, s));
+    sr.finish();
+    SHELFI_HIP(hipStreamSynchronize(s));
+    if (ctx->host_flag[6])
+      throw Error{SHELFI_ERR_FORMAT, "ciphertext residue >= its tower modulus (malformed batch)"};
   });
 }
 

@@ -379,6 +379,14 @@ __device__ __noinline__ uint32_t chacha20_word(Key8 key, uint64_t counter, uint6
 }
 // |e| and sign from a 32-bit word, tab_hi / tab_lo = the CDT's top 31 / low 32 bits, padded to
 // 64 entries with 0xFFFFFFFF tops (above every 31-bit value); lo32() fetches the tie word.
+// load_cdt32 stages the two tables (64 entries each, LDS) from the first 64 threads of a workgroup.
+__device__ __forceinline__ void load_cdt32(const uint64_t* __restrict__ cdt, int T, uint32_t* hi, uint32_t* lo) {
+  if (threadIdx.x < 64) {
+    const uint64_t v = (int)threadIdx.x < T ? cdt[threadIdx.x] : ~0ull;
+    hi[threadIdx.x] = (int)threadIdx.x < T ? (uint32_t)(v >> 32) : 0xFFFFFFFFu;
+    lo[threadIdx.x] = (uint32_t)v;
+  }
+}
 template <class Lo>
 __device__ __forceinline__ int64_t gauss32(uint32_t w, const uint32_t* tab_hi, const uint32_t* tab_lo, Lo lo32) {
   const uint32_t H = w >> 1;

@@ -190,14 +190,6 @@ __global__ __launch_bounds__(1024) void fft_inv_whole(const double* __restrict__
 // N/2 + i*gap (imaginary part) (CKKSPackedEncoding::Encode layout).  Output is the
 // compact per-coefficient record {int64 m + e0, int16 (e1 << 8) | (uint8)v} — 10 bytes
 // instead of the 3 L residues the NTT needs, which ntt_fwd_cols_enc expands per tower.
-__device__ __forceinline__ void load_cdt32(const uint64_t* __restrict__ cdt, int T, uint32_t* hi, uint32_t* lo) {
-  if (threadIdx.x < 64) {
-    const uint64_t v = (int)threadIdx.x < T ? cdt[threadIdx.x] : ~0ull;
-    hi[threadIdx.x] = (int)threadIdx.x < T ? (uint32_t)(v >> 32) : 0xFFFFFFFFu;
-    lo[threadIdx.x] = (uint32_t)v;
-  }
-}
-
 // Encode's range flag (GenFlag words): [0] = a |x Delta| above 2^61 (a finite one: the call is redone on
 // the large-value path, launch_encrypt_approx), [1] = a non-finite value (refused).
 __device__ __forceinline__ void enc_range_flag(GenFlag f, double val) {

@@ -244,6 +244,7 @@ struct shelfi_ctx {
   std::vector<uint64_t> pk_host, sk_host;
   bool keys_loaded = false;
   bool palisade_keys = false;
+  bool threshold_share = false;  // the secret is a share from shelfi_multiparty_keygen: no symmetric encrypt
   uint64_t key_id = 0;
   uint64_t params_id = 0;
   uint64_t seed = 0;          // 0 -> OS entropy per call
@@ -285,7 +286,7 @@ struct shelfi_ctx {
   bool log_error_pending = false;  // dev_flag[2] holds a newer one, read on demand (shelfi_decode_log_error)
   std::string pal_ctx_obj;       // PALISADE keys: embedded context object (§8 f1)
   std::string pal_keytag;        // PALISADE keys: key tag
-  int wire = 0;                  // encrypt output: 0 blob, 1 PALISADE archive
+  int wire = 0;                  // encrypt output: 0 blob, 1 PALISADE archive, 2 packed blob, 3 seeded blob
   // device weight-limb buffers of wavg_packed (ring; reused while weights repeat)
   static constexpr int kWeightRing = 8;
   uint32_t* wl_dev[kWeightRing] = {};
@@ -357,6 +358,10 @@ void launch_blob_pack(const uint64_t* src, uint64_t K, uint32_t L, uint32_t logN
                       const TowerConst* tc, uint32_t* dst, uint32_t* bad, hipStream_t s);
 void launch_blob_unpack(const uint32_t* src, uint64_t K, uint32_t L, uint32_t logN, const ArenaPack& ap,
                         uint64_t* dst, hipStream_t s);
+// The kernel behind it: G polynomial groups (L towers each), the outputs gstride words apart -- L N for a packed
+// blob, 2 L N for a seeded blob's c0 groups into polynomial 0 of a [G][2][L][N] batch
+void launch_blob_unpack_groups(const uint32_t* src, uint64_t G, uint32_t L, uint32_t logN, const ArenaPack& ap,
+                               uint64_t* dst, uint64_t gstride, hipStream_t s);
 // Residue runs of an upload landed raw (a PALISADE archive's byte range with its tower headers): run j is
 // run_bytes bytes at raw + src_off[j] (any alignment) -> dst + j * run_bytes (16-B aligned)
 void launch_gather_runs(const uint8_t* raw, const uint64_t* src_off, uint64_t runs, uint32_t run_bytes, uint8_t* dst,
@@ -432,6 +437,19 @@ void launch_plain_op(int op, const uint64_t* ct, const uint64_t* pt, uint64_t K,
 // out = a - b mod q_t, or -a when b is null, over rows = K * 2 * Ll polynomials (out may be an input)
 void launch_ct_sub(const uint64_t* a, const uint64_t* b, uint64_t rows, uint32_t Ll, uint32_t logN,
                    const TowerConst* tq, uint64_t* out, hipStream_t s);
+// ---- seeded ciphertexts (seeded.hip) ----
+// Symmetric encrypt of n doubles -> c0 [K][L][N] (EVALUATION, canonical) of the seeded ciphertexts
+// k0 .. k0 + K - 1 of a blob whose public seed is `seed`: c0 = NTT(m + e0) - a . NTT(s), e0 the public-key
+// encrypt's at stream key `key` and index g0 + k, a the seed's stream (never stored).  scratch =
+// seeded_encrypt_scratch_bytes(p, K).  GenFlag words 0 / 1 as launch_encode_plain's.
+constexpr uint64_t kSeededMaxCts = 1ull << 48;  // the c1 stream's nonce holds the ciphertext index in 48 bits
+size_t seeded_encrypt_scratch_bytes(const Params& p, uint64_t K);
+void launch_encrypt_seeded(const Params& p, const DeviceTables& dt, const DeviceKeys& dk, const double* x, uint64_t n,
+                           uint64_t K, uint64_t* c0, void* scratch, const uint32_t key[8], uint64_t g0,
+                           const uint32_t seed[8], uint64_t k0, GenFlag flag, hipStream_t s);
+// Polynomial 1 of a [kn][2][Lu][N] batch <- the seed's stream of ciphertexts k0 .. k0 + kn - 1, towers [0, Lu)
+void launch_seeded_expand(const uint32_t seed[8], uint64_t k0, uint64_t kn, uint32_t Lu, uint32_t logN,
+                          const TowerConst* tc, uint64_t* ct, hipStream_t s);
 // Decode noise flooding (PALISADE 1.11 Decode); off = exact decode.
 struct DecodeNoise {
   int enabled = 0;
@@ -493,6 +511,8 @@ void eval_release(shelfi_ctx* ctx, bool keys_only);
 void load_evalkey_if_present(shelfi_ctx* ctx, const std::string& dir);
 // context.cpp: refuse a call that needs keys before they are loaded
 void require_keys(const shelfi_ctx* ctx);
+// ... and that the secret key is whole, not a threshold share (the seeded encrypt)
+void require_own_secret(const shelfi_ctx* ctx);
 
 // ---- EvalMult (ct x ct) + relinearization, ModReduce (keyswitch.hip) ----
 // PALISADE 1.11 HYBRID key switching: Q_l split into digits of alpha towers, special

@@ -610,15 +610,19 @@ __device__ __forceinline__ void unpack_row(const uint32_t* __restrict__ sl, uint
   }
 }
 
+// The output's polynomial groups (L towers, rpg rows each) lie gstride words apart: L N for a packed blob's
+// [K][2][L][N], 2 L N for a seeded blob's c0 groups, which land in polynomial 0 of their ciphertexts.
 __global__ __launch_bounds__(64 * kPackedWaves) void blob_unpack_kernel(const uint32_t* __restrict__ src,
                                                                        uint64_t rows, uint32_t L, uint32_t logN,
-                                                                       ArenaPack ap, uint64_t* __restrict__ dst) {
+                                                                       ArenaPack ap, uint64_t* __restrict__ dst,
+                                                                       uint64_t gstride) {
   const uint64_t r = (uint64_t)blockIdx.x * kPackedWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (r >= rows) return;
   const uint32_t lane = threadIdx.x & 63;
   const PackedRow pr = packed_row(r, 1, L, logN, ap);
   const uint32_t* __restrict__ sl = src + pr.base;
-  uint64_t* __restrict__ o = dst + r * kArenaChunk;
+  const uint64_t rpg = (uint64_t)L << (logN - 9), g = r / rpg;
+  uint64_t* __restrict__ o = dst + g * gstride + (r - g * rpg) * kArenaChunk;
   switch (pr.U) {
 #define UPR(UU) \
   case UU: unpack_row<UU>(sl, o, lane); break;
@@ -626,6 +630,17 @@ __global__ __launch_bounds__(64 * kPackedWaves) void blob_unpack_kernel(const ui
 #undef UPR
     default: break;
   }
+}
+
+void launch_blob_unpack_groups(const uint32_t* src, uint64_t G, uint32_t L, uint32_t logN, const ArenaPack& ap,
+                               uint64_t* dst, uint64_t gstride, hipStream_t s) {
+  const uint64_t rows = G * L << (logN - 9);
+  if (!rows) return;
+  const uint64_t blocks = (rows + kPackedWaves - 1) / kPackedWaves;
+  if (blocks > 0x7FFFFFFFull) throw Error{SHELFI_ERR_ARG, "blob too large"};
+  hipLaunchKernelGGL(blob_unpack_kernel, dim3((uint32_t)blocks), dim3(64 * kPackedWaves), 0, s, src, rows, L, logN,
+                     ap, dst, gstride);
+  SHELFI_HIP(hipGetLastError());
 }
 
 void launch_blob_pack(const uint64_t* src, uint64_t K, uint32_t L, uint32_t logN, const ArenaPack& ap,
@@ -636,13 +651,7 @@ void launch_blob_pack(const uint64_t* src, uint64_t K, uint32_t L, uint32_t logN
 
 void launch_blob_unpack(const uint32_t* src, uint64_t K, uint32_t L, uint32_t logN, const ArenaPack& ap,
                         uint64_t* dst, hipStream_t s) {
-  const uint64_t rows = K * 2 * L << (logN - 9);
-  if (!rows) return;
-  const uint64_t blocks = (rows + kPackedWaves - 1) / kPackedWaves;
-  if (blocks > 0x7FFFFFFFull) throw Error{SHELFI_ERR_ARG, "blob too large"};
-  hipLaunchKernelGGL(blob_unpack_kernel, dim3((uint32_t)blocks), dim3(64 * kPackedWaves), 0, s, src, rows, L, logN,
-                     ap, dst);
-  SHELFI_HIP(hipGetLastError());
+  launch_blob_unpack_groups(src, 2 * K, L, logN, ap, dst, (uint64_t)L << logN, s);
 }
 
 // The direct uploads' gather (round 5): 16 output bytes per thread from 5 aligned dwords of the raw

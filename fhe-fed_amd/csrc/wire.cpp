@@ -20,8 +20,9 @@ static BlobHeader parse_blob(const uint8_t* blob, size_t len, const shelfi_ctx* 
   BlobHeader h;
   std::memcpy(&h, blob, sizeof(h));
   // version 1: uint64 residues [K][2][L][N]; version 2: the packed wire payload (the arena's slice
-  // format with C = 1, U_t bits per residue: DESIGN.md §3, §5.3)
-  if (std::memcmp(h.magic, "SHCT", 4) != 0 || (h.version != 1 && h.version != 2) || h.header_bytes != 64)
+  // format with C = 1, U_t bits per residue: DESIGN.md §3, §5.3); version 3: seeded -- 64 more bytes (the
+  // 32-byte public seed, 32 zero bytes), then each ciphertext's c0 as one version-2 group
+  if (std::memcmp(h.magic, "SHCT", 4) != 0 || h.version < 1 || h.version > 3 || h.header_bytes != 64)
     throw Error{SHELFI_ERR_FORMAT, "not a SHELFI ciphertext blob (bad magic/version)"};
   if (h.L == 0 || h.L > kMaxTowers || h.logN < 10 || h.logN > 17)
     throw Error{SHELFI_ERR_FORMAT, "corrupt ciphertext blob header"};
@@ -29,11 +30,18 @@ static BlobHeader parse_blob(const uint8_t* blob, size_t len, const shelfi_ctx* 
     if (h.logN != ctx->p.logN || h.L != ctx->p.L || h.params_id != ctx->params_id)
       throw Error{SHELFI_ERR_FORMAT, "ciphertext was produced under different crypto parameters"};
   }
-  const uint64_t payload = len - sizeof(BlobHeader);
-  if (h.version == 2 && !ctx) {
-    // without a context the packed widths are unknown: a ciphertext is 2 (N / 512) rows of 64 U
-    // bytes for some 32 L <= U <= 60 L
-    const uint64_t unit = 2ull * (1ull << (h.logN - 9)) * 64;
+  const size_t lead = h.version == 3 ? kSeededLeadBytes : sizeof(BlobHeader);
+  if (len < lead) throw Error{SHELFI_ERR_FORMAT, "ciphertext blob too short"};
+  if (h.version == 3) {
+    for (size_t i = sizeof(BlobHeader) + 32; i < lead; ++i)
+      if (blob[i]) throw Error{SHELFI_ERR_FORMAT, "seeded ciphertext blob: non-zero padding after the seed"};
+    if (h.K >= kSeededMaxCts) throw Error{SHELFI_ERR_FORMAT, "seeded ciphertext blob: 2^48 ciphertexts or more"};
+  }
+  const uint64_t payload = len - lead;
+  if (h.version != 1 && !ctx) {
+    // without a context the packed widths are unknown: a ciphertext is 2 (N / 512) rows (seeded: N / 512,
+    // its c0 alone) of 64 U bytes for some 32 L <= U <= 60 L
+    const uint64_t unit = (h.version == 3 ? 1ull : 2ull) * (1ull << (h.logN - 9)) * 64;
     bool ok = h.K ? payload % h.K == 0 : payload == 0;
     if (ok && h.K) {
       const uint64_t per = payload / h.K;
@@ -44,8 +52,10 @@ static BlobHeader parse_blob(const uint8_t* blob, size_t len, const shelfi_ctx* 
   }
   // K comes from an untrusted header: bound it by the payload before multiplying, so a
   // forged K whose K * ct_bytes wraps mod 2^64 cannot pass the length check.
-  const uint64_t ct_bytes = h.version == 1 ? 2ull * h.L * (8ull << h.logN) : arena_ct_words(ctx->p, 1) * 8;
-  if (h.K > payload / ct_bytes || len != sizeof(BlobHeader) + h.K * ct_bytes)
+  const uint64_t ct_bytes = h.version == 1   ? 2ull * h.L * (8ull << h.logN)
+                            : h.version == 2 ? arena_ct_words(ctx->p, 1) * 8
+                                             : packed_poly_bytes(ctx->p, ctx->p.L);
+  if (h.K > payload / ct_bytes || len != lead + h.K * ct_bytes)
     throw Error{SHELFI_ERR_FORMAT, "ciphertext blob length does not match header"};
   return h;
 }
@@ -135,6 +145,8 @@ CtLayout open_cts(const shelfi_ctx* ctx, const uint8_t* b, size_t len) {
   }
   BlobHeader h = parse_blob(b, len, ctx);
   v.packed = h.version == 2;
+  v.seeded = h.version == 3;
+  if (v.seeded) std::memcpy(v.seed, b + sizeof(BlobHeader), 32);  // eight little-endian words
   v.K = h.K;
   v.depth = h.depth;
   v.level = h.level;
@@ -146,12 +158,14 @@ CtLayout open_cts(const shelfi_ctx* ctx, const uint8_t* b, size_t len) {
 
 // Size of (and, with buf, the header / framing of) an output batch in format fmt; returns its layout.
 CtLayout make_output(const shelfi_ctx* ctx, int fmt, uint64_t K, uint32_t depth, uint64_t level, double scale,
-                     uint8_t* buf, size_t* total) {
+                     uint8_t* buf, size_t* total, const uint32_t* seed) {
   const bool pal = fmt == 1;
   CtLayout v;
+  if (seed) std::memcpy(v.seed, seed, sizeof(v.seed));
   v.base = buf;
   v.pal = pal;
   v.packed = fmt == 2;
+  v.seeded = fmt == 3;
   v.K = K;
   v.depth = depth;
   v.level = level;
@@ -165,11 +179,18 @@ CtLayout make_output(const shelfi_ctx* ctx, int fmt, uint64_t K, uint32_t depth,
                             4, true, true, buf, total);
     return v;
   }
-  *total = sizeof(BlobHeader) + K * (v.packed ? 2 * packed_poly_bytes(p, p.L) : 2ull * p.L * p.N * 8);
+  if (v.seeded && K >= kSeededMaxCts) throw Error{SHELFI_ERR_ARG, "seeded wire format: 2^48 ciphertexts or more"};
+  *total = v.seeded ? kSeededLeadBytes + K * packed_poly_bytes(p, p.L)
+                    : sizeof(BlobHeader) + K * (v.packed ? 2 * packed_poly_bytes(p, p.L) : 2ull * p.L * p.N * 8);
   if (buf) {
     BlobHeader h = make_header(ctx, K, depth, scale);
     if (v.packed) h.version = 2;
+    if (v.seeded) h.version = 3;
     std::memcpy(buf, &h, sizeof(h));
+    if (v.seeded) {  // the seed, then the padding that keeps the payload's alignment
+      std::memcpy(buf + sizeof(h), v.seed, 32);
+      std::memset(buf + sizeof(h) + 32, 0, kSeededLeadBytes - sizeof(h) - 32);
+    }
   }
   return v;
 }
@@ -177,6 +198,11 @@ CtLayout make_output(const shelfi_ctx* ctx, int fmt, uint64_t K, uint32_t depth,
 }  // namespace shelfi
 
 extern "C" {
+
+int shelfi_blob_version(const uint8_t* blob, size_t len, uint32_t* version) {
+  if (!version) return SHELFI_ERR_ARG;
+  return guarded([&] { *version = parse_blob(blob, len, nullptr).version; });
+}
 
 int shelfi_blob_info(const uint8_t* blob, size_t len, uint64_t* num_cts, uint32_t* depth,
                      double* scale, uint64_t* key_id) {
@@ -252,6 +278,8 @@ int shelfi_blob_unpack(const shelfi_ctx* ctx, const uint8_t* blob, size_t len, u
       std::memcpy(out, pay, h.K * 2ull * p.L * p.N * 8);
       return;
     }
+    if (h.version == 3)  // c1 is a ChaCha20 stream, which the host does not run
+      throw Error{SHELFI_ERR_ARG, "a seeded blob is expanded on the device: use shelfi_dev_blob_unpack (device.from_blob)"};
     const ArenaPack ap = arena_pack(p);
     const uint32_t rpt = p.N / kArenaChunk;
     size_t off = 0;  // dwords
@@ -307,7 +335,7 @@ int shelfi_blob_pack(const shelfi_ctx* ctx, const uint64_t* residues, uint64_t K
 
 // ------------------------------------------------- PALISADE wire format ----
 int shelfi_set_wire_format(shelfi_ctx* ctx, int format) {
-  if (!ctx || format < 0 || format > 2) return SHELFI_ERR_ARG;
+  if (!ctx || format < 0 || format > 3) return SHELFI_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   return guarded([&] {
     if (format == 1 && ctx->pal_ctx_obj.empty())

@@ -38,14 +38,15 @@ namespace {
 std::unique_ptr<CKKS> make_ckks(const std::string& scheme, unsigned batchSize, unsigned scaleFactorBits,
                                 const std::string& cryptodir, unsigned multDepth, uint64_t seed, bool decodeNoise,
                                 const std::string& wireFormat, int device) {
-  if (wireFormat != "palisade" && wireFormat != "shelfi" && wireFormat != "packed")
-    throw py::value_error("wireFormat must be 'palisade', 'shelfi' or 'packed'");
+  if (wireFormat != "palisade" && wireFormat != "shelfi" && wireFormat != "packed" && wireFormat != "seeded")
+    throw py::value_error("wireFormat must be 'palisade', 'shelfi', 'packed' or 'seeded'");
   CKKS::Options o;
   o.multDepth = multDepth;
   o.seed = seed;
   o.decodeNoise = decodeNoise;
   o.wire_palisade = wireFormat == "palisade";
   o.wire_packed = wireFormat == "packed";
+  o.wire_seeded = wireFormat == "seeded";
   o.device = device;
   return std::make_unique<CKKS>(scheme, batchSize, scaleFactorBits, cryptodir, o);
 }

@@ -155,13 +155,19 @@ int shelfi_decode_log_error(shelfi_ctx* ctx, int* log_error);
 /* Blob inspection: number of ciphertexts, depth, scale, key id. */
 int shelfi_blob_info(const uint8_t* blob, size_t len, uint64_t* num_cts, uint32_t* depth,
                      double* scale, uint64_t* key_id);
+/* Beside shelfi_blob_info (what a receiver reads before the Deserial of ckks.cpp:281): the blob's version --
+ * 1 uint64 residues, 2 packed, 3 seeded (shelfi_set_wire_format's 0, 2 and 3).  Header and length are checked
+ * as shelfi_blob_info checks them. */
+int shelfi_blob_version(const uint8_t* blob, size_t len, uint32_t* version);
 /* Build a blob from raw residues [K][2][L][N] (host) with the given metadata. */
 int shelfi_blob_pack(const shelfi_ctx* ctx, const uint64_t* residues, uint64_t num_cts,
                      uint32_t depth, double scale, uint8_t** out, size_t* out_len);
 /* Offset of the residue payload inside a blob (64-byte header). */
 size_t shelfi_blob_header_bytes(void);
 /* Host-only: a blob's residues as [K][2][L][N] uint64 (out: K*2*L*N words) — a version-1 payload
- * copied, a version-2 (packed wire, shelfi_set_wire_format 2) payload unpacked. */
+ * copied, a version-2 (packed wire, shelfi_set_wire_format 2) payload unpacked.  A version-3 (seeded)
+ * blob is refused (SHELFI_ERR_ARG): its c1 is a ChaCha20 stream, expanded on the device by
+ * shelfi_dev_blob_unpack. */
 int shelfi_blob_unpack(const shelfi_ctx* ctx, const uint8_t* blob, size_t len, uint64_t* out);
 
 /* ---- PALISADE 1.11 wire format -------------- */
@@ -185,9 +191,18 @@ typedef struct {
  * are generated or loaded in PALISADE's files, as ckks.cpp:98-103 writes them), 2 packed blob
  * (version 2: the residues at their moduli's widths, the arena's slice format with C = 1 — 218 of
  * 256 bits per coefficient at 2^15/L4, so a PCIe-bound upload carries 15% fewer bytes; DESIGN.md
- * §5.3).  Every entry that takes ciphertext bytes accepts all three. */
+ * §5.3), 3 seeded blob (version 3, DESIGN.md §2.17: beside cc->Encrypt (ckks.cpp:81), for learners that
+ * hold the secret key as the reference's do -- encrypt is symmetric, c1 = a is expanded from a 32-byte
+ * public seed by whoever reads the blob, and only c0 travels, packed: 892,928 bytes a ciphertext at
+ * 2^15/L4 where the packed blob has 1,785,856.  The blob is the 64-byte header, the seed, 32 zero bytes,
+ * then one packed group (c0) a ciphertext.  encrypt then needs the whole secret key: SHELFI_ERR_STATE on
+ * a context whose secret is a threshold share (shelfi_multiparty_keygen), SHELFI_ERR_RANGE for a
+ * coefficient above 2^61 (no large-value path).  The seed is public; two encryptions under one (seed,
+ * ciphertext index) leak the difference of their messages, so a seed is drawn per call).  Every entry
+ * that takes ciphertext bytes accepts all four; computeWeightedAverage answers seeded inputs (all learners
+ * seeded, or none) in format 2: a sum of seeded ciphertexts is not seeded. */
 int shelfi_set_wire_format(shelfi_ctx* ctx, int format);
-/* The format encrypt answers in right now (0, 1 or 2; -1 for a NULL context). */
+/* The format encrypt answers in right now (0 .. 3; -1 for a NULL context). */
 int shelfi_get_wire_format(const shelfi_ctx* ctx);
 /* Host-only: parse an archive; residues [K][2][L][N] copied out when non-NULL. */
 int shelfi_palisade_parse(const uint8_t* archive, size_t len, shelfi_palisade_info* info,
@@ -529,6 +544,27 @@ int shelfi_dev_add(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev
  * SHELFI_DEV_CHUNK_MIB (16 * batch + 64 bytes per plaintext) and synchronises `stream` before returning. */
 int shelfi_dev_encode(shelfi_ctx* ctx, const double* x_dev, size_t n, uint32_t towers, double scale,
                       uint64_t* pt_dev, void* stream);
+/* ---- seeded ciphertexts on the device ---- */
+/* Beside cc->Encrypt (ckks.cpp:81): the symmetric encrypt of n doubles into K = ceil(n / batch) seeded
+ * ciphertexts -- c0_dev [K][L][N] = NTT(m + e) - a . NTT(s), EVALUATION, canonical, and the call's public
+ * seed (32 bytes) from which shelfi_dev_expand_seeded draws c1 = a for ciphertext indices 0 .. K - 1.  e is
+ * the e0 of shelfi_dev_encrypt at the same seed and index.  Needs the whole secret key (SHELFI_ERR_STATE
+ * without keys or on a threshold share); a coefficient above 2^61 or a non-finite value is
+ * SHELFI_ERR_RANGE.  Synchronises `stream` before returning. */
+int shelfi_dev_encrypt_seeded(shelfi_ctx* ctx, const double* x_dev, size_t n, uint64_t* c0_dev, uint8_t seed_out[32],
+                              void* stream);
+/* Polynomial 1 of the batch ct_dev [K][2][towers][N] <- the stream of `seed` for ciphertext indices
+ * k0 .. k0 + K - 1 and towers [0, towers): word j of tower t is the 128-bit draw (keygen's) of the
+ * ChaCha20 block with key = seed, counter j >> 2, nonce (9 << 56) | (k << 8) | t, mod q_t.  Polynomial 0
+ * is left as it is (the caller's c0).  Indices reach 2^48 - 1.  Needs no key; enqueued on `stream`. */
+int shelfi_dev_expand_seeded(shelfi_ctx* ctx, uint64_t* ct_dev, size_t K, uint32_t towers, const uint8_t seed[32],
+                             uint64_t k0, void* stream);
+/* Beside the Deserial of ckks.cpp:281: ciphertext bytes in any wire format (host) -> the batch
+ * [K][2][L][N] at out_dev, K the blob's count (shelfi_blob_info); a seeded blob's c1 is expanded.  The
+ * header is checked against the context and every landed residue against its modulus
+ * (SHELFI_ERR_FORMAT).  Synchronises `stream` before returning. */
+int shelfi_dev_blob_unpack(shelfi_ctx* ctx, const uint8_t* blob, size_t len, size_t K, uint64_t* out_dev,
+                           void* stream);
 /* cc->EvalMult(ct, pt): both components times the plaintext; ct_dev, out_dev [K][2][towers][N], pt_dev
  * [Kp][towers][N] with Kp = K, or Kp = 1 (one plaintext for every ciphertext); any other Kp is
  * SHELFI_ERR_ARG.  Scale: scale_ct * scale_pt.  This and the four calls below need no scratch and

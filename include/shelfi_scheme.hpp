@@ -85,6 +85,7 @@ class CKKS : public Scheme {
     bool decodeNoise = true;    // PALISADE 1.11's decode noise flooding (its Decrypt floods)
     bool wire_palisade = true;  // encrypt / aggregate answer in PALISADE's cereal archives
     bool wire_packed = false;   // with wire_palisade false: packed library blobs (version 2)
+    bool wire_seeded = false;   // with both false: seeded library blobs (version 3; the learner holds the secret key)
   };
 
   CKKS(std::string scheme, unsigned batchSize, unsigned scaleFactorBits, std::string cryptodir)
@@ -233,7 +234,7 @@ class CKKS : public Scheme {
   // keys generated here or loaded from PALISADE files carry the context object and key tag
   // PALISADE's archive format needs
   void apply_wire_format() {
-    throw_on_error(shelfi_set_wire_format(ctx_, opt_.wire_palisade ? 1 : opt_.wire_packed ? 2 : 0), "wire format");
+    throw_on_error(shelfi_set_wire_format(ctx_, opt_.wire_palisade ? 1 : opt_.wire_packed ? 2 : opt_.wire_seeded ? 3 : 0), "wire format");
   }
 
   unsigned batchSize;
