@@ -182,6 +182,8 @@ SIGNATURES = {
                                   C.c_void_p]),
     "shelfi_gram_pairs": (C.c_size_t, [C.c_size_t]),
     "shelfi_gram_slice_count": (C.c_uint64, [C.c_void_p]),
+    "shelfi_dev_wsum_ct": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, C.c_uint32,
+                                     C.POINTER(C.c_void_p), C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "shelfi_dev_project": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t,
                                      C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "shelfi_dotp_slice_count": (C.c_uint64, [C.c_void_p]),

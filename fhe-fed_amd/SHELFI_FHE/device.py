@@ -555,6 +555,68 @@ def gram(ckks, batches, out=None):
     return out
 
 
+WSUM_MAX_LEARNERS = 32  # shelfi_dev_wsum_ct: as GRAM_MAX_BATCHES, for the updates and for the weights
+
+
+def _unstack(t, what):
+    if hasattr(t, "dim"):
+        if t.dim() != 5 or not t.is_contiguous():
+            raise ValueError("a stacked %s operand must be a contiguous [C][K][2][l][N] tensor" % what)
+        return [t[i] for i in range(t.shape[0])]
+    return list(t)
+
+
+def wsum_ct(ckks, batches, weights, out=None):
+    """EvalLinearWSum with ENCRYPTED weights (needs ckks.evalMultKeyGen()): out[k] = sum_c weights[c] * batches[c][k]
+    over C learners, with one key switch per output ciphertext instead of one per product.  batches: a sequence of
+    1..32 update tensors [K][2][lu][N], or one stacked [C][K][2][lu][N] tensor; weights: as many tensors
+    [Kw][2][l][N], or one stacked tensor, with Kw = 1 (one weight ciphertext for a learner's whole update) or Kw = K
+    (one per update ciphertext).  The result [K][2][l][N] is, bit for bit, dot() of the stacked weights against the
+    stacked k-th update ciphertexts, and at C = 1 mult(weight, update).  out must overlap no input.
+    Scale: scale_w * scale_u, depth 2: rescale() it as a mult() result, then add / decrypt / partial_decrypt.
+    Level rule: lu >= l.  Weights that come out of a computation sit lower than fresh updates; the first l towers of
+    every update polynomial are read in place (dropping towers of an RNS ciphertext is only a stride), and the result
+    sits at the weights' level l."""
+    torch = _torch()
+    batches, weights = _unstack(batches, "update"), _unstack(weights, "weight")
+    n = len(batches)
+    if not 1 <= n <= WSUM_MAX_LEARNERS:
+        raise ValueError("EvalLinearWSum needs 1..%d learners" % WSUM_MAX_LEARNERS)
+    if len(weights) != n:
+        raise ValueError("EvalLinearWSum needs one weight batch per update batch")
+    u, w = batches[0], weights[0]
+    _check_ct(u, ckks, any_level=True)
+    _check_ct(w, ckks, any_level=True)
+    for b in batches[1:]:
+        _check_ct(b, ckks, any_level=True)
+        if b.shape != u.shape:
+            raise ValueError("EvalLinearWSum updates must have the same shape (same level)")
+    for b in weights[1:]:
+        _check_ct(b, ckks, any_level=True)
+        if b.shape != w.shape:
+            raise ValueError("EvalLinearWSum weights must have the same shape (same level)")
+    if any(b.device != u.device for b in batches + weights):
+        raise ValueError("EvalLinearWSum operands must live on the same device")
+    K, _, lu, N = u.shape
+    Kw, _, l, _ = w.shape
+    if K == 0:  # (an empty tensor has no storage to hand the library, which refuses K = 0 by name)
+        raise ValueError("EvalLinearWSum needs at least one update ciphertext a learner")
+    if Kw not in (1, K):
+        raise ValueError("EvalLinearWSum weights are [1 or K][2][l][N]: one ciphertext for all updates, or one each")
+    if l > lu:
+        raise ValueError("EvalLinearWSum updates must sit at the weights' level or above")
+    if out is None:
+        out = torch.empty((K, 2, l, N), dtype=u.dtype, device=u.device)
+    _check_ct(out, ckks, K, any_level=True)
+    if tuple(out.shape) != (K, 2, l, N) or out.device != u.device:
+        raise ValueError("out must be a contiguous [K][2][l][N] 64-bit tensor at the weights' level on the operands' device")
+    up = (C.c_void_p * n)(*[b.data_ptr() for b in batches])
+    wp = (C.c_void_p * n)(*[b.data_ptr() for b in weights])
+    check(_lib.load().shelfi_dev_wsum_ct(ckks._ctx, up, n, K, int(lu), wp, Kw, int(l), C.c_void_p(out.data_ptr()),
+                                         C.c_void_p(_stream_ptr(u))), "dev_wsum_ct")
+    return out
+
+
 def gram_sq_distances(ckks, G, n: int, out=None):
     """Krum's input from gram()'s result G [P][2][l][N] over n batches: the n (n - 1) / 2 ciphertexts
     G_ii + G_jj - 2 G_ij of ||u_i - u_j||^2 for i < j, in gram_pairs(n)'s order without the diagonal.  Index

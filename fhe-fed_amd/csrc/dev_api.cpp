@@ -1,7 +1,8 @@
 // dev_api.cpp — the device API (shelfi_dev_*: device buffers in, device buffers out, the caller's
 // stream): aggregation of separate batches, encrypt / decrypt and their threshold forms, the plaintext
 // operands, and the evaluation calls (EvalMult, EvalInnerProduct, the Gram matrix, ModReduce, Rotate, EvalSum,
-// EvalInnerProduct(ct, pt), EvalAdd / Sub / Negate).  The packed resident arena is dev_arena.cpp.
+// EvalInnerProduct(ct, pt), EvalLinearWSum with encrypted weights, EvalAdd / Sub / Negate; DESIGN.md §2.11,
+// §2.13 - §2.16, §2.18).  The packed resident arena is dev_arena.cpp.
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -511,6 +512,50 @@ uint64_t shelfi_gram_slice_count(const shelfi_ctx* ctx) {
   if (!ctx) return 0;
   std::lock_guard<std::mutex> lk(ctx->mu);
   return ctx->gram_slice_count;
+}
+
+// EvalLinearWSum with encrypted weights (wsum.hip): the K output ciphertexts cut into chains under
+// SHELFI_EVAL_CHUNK_MIB as shelfi_dev_mult's, a chain the summed-tensor pass over its share of every learner's
+// batch and one key switch of its ciphertexts
+int shelfi_dev_wsum_ct(shelfi_ctx* ctx, const uint64_t* const* batches_dev, size_t C, size_t K, uint32_t u_towers,
+                       const uint64_t* const* weights_dev, size_t Kw, uint32_t towers, uint64_t* out_dev,
+                       void* stream) {
+  if (!ctx || !batches_dev || !weights_dev || !out_dev) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    if (C < 1 || C > (size_t)kWsumMaxLearners) throw Error{SHELFI_ERR_ARG, "EvalLinearWSum needs 1..32 learners"};
+    for (size_t i = 0; i < C; ++i)
+      if (!batches_dev[i] || !weights_dev[i]) throw Error{SHELFI_ERR_ARG, "EvalLinearWSum: null batch"};
+    DeviceGuard g(ctx->device);
+    // a chain that cannot key-switch says so, before the key it can never hold is missed
+    if (!eval_state(ctx).ks_error.empty()) throw Error{SHELFI_ERR_ARG, eval_state(ctx).ks_error};
+    if (!ctx->ev || !ctx->ev->evk)
+      throw Error{SHELFI_ERR_STATE, "no evaluation key: call evalMultKeyGen() first"};
+    if (towers < 1 || towers > u_towers || u_towers > ctx->p.L)
+      throw Error{SHELFI_ERR_ARG, "EvalLinearWSum: 1 <= towers <= u_towers <= L (the updates sit at the weights' level or above)"};
+    LevelState& l = level(ctx, towers);
+    if (!K) throw Error{SHELFI_ERR_ARG, "EvalLinearWSum needs at least one update ciphertext a learner"};
+    if (Kw != 1 && Kw != K)
+      throw Error{SHELFI_ERR_ARG, "EvalLinearWSum: one weight ciphertext per update ciphertext, or one for all"};
+    // every input is read by every chain's first pass: the output lies apart from all of them -- from an update
+    // batch over the u_towers towers it is stored with, not only the ones read
+    const uint32_t N = ctx->p.N;
+    const uint64_t ctw = 2ull * towers * N, uctw = 2ull * u_towers * N;
+    for (size_t i = 0; i < C; ++i)
+      if (words_overlap(batches_dev[i], uctw * K, out_dev, ctw * K) ||
+          words_overlap(weights_dev[i], ctw * Kw, out_dev, ctw * K))
+        throw Error{SHELFI_ERR_ARG, "EvalLinearWSum output must not overlap the inputs"};
+    const KsArgs& a = l.args;
+    hipStream_t s = (hipStream_t)stream;
+    const auto bytes_of = [&](uint64_t kc) { return ks_scratch(a, N, kc); };
+    const uint64_t chains =
+        for_chunks(ctx, K, switches().eval_chunk_mib, bytes_of, [&](uint64_t k0, uint64_t kc, void* scratch) {
+          launch_wsum(a, ctx->dt, l.ext, l.dtf, ctx->ev->evk, ctx->ev->evk_sh, batches_dev, u_towers, weights_dev,
+                      Kw == K && K > 1, (uint32_t)C, k0, kc, out_dev, scratch, s);
+        });
+    SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
+    ctx->eval_chunk_count = chains;
+  });
 }
 
 // EvalInnerProduct(ct, pt) (dotp.hip): no key and one launch chain whatever C, R and K are -- the

@@ -278,7 +278,7 @@ struct shelfi_ctx {
   int decode_exact = 0;          // shelfi_set_decode_exact: every decrypt over every tower, exact CRT
   uint64_t decode_redo_count = 0;  // decrypt calls whose fast pass was redone exactly (shelfi_decode_redo_count)
   uint64_t encode_redo_count = 0;  // encrypt calls redone on the large-value path (shelfi_encode_redo_count)
-  uint64_t eval_chunk_count = 0;   // launch chains of the last mult / gram / rescale / rotate / eval_sum (shelfi_eval_chunk_count)
+  uint64_t eval_chunk_count = 0;   // launch chains of the last mult / gram / wsum_ct / rescale / rotate / eval_sum (shelfi_eval_chunk_count)
   uint64_t dot_slice_count = 0;    // slices of the last successful dot (shelfi_dot_slice_count)
   uint64_t gram_slice_count = 0;   // slices of the last successful gram (shelfi_gram_slice_count)
   uint64_t dotp_slice_count = 0;   // slices of the last successful project (shelfi_dotp_slice_count)
@@ -587,6 +587,16 @@ uint32_t dotp_slices(uint64_t C, uint64_t R, uint64_t K, uint32_t Ll, uint32_t l
                      uint64_t budget_bytes);
 void launch_dotp(const uint64_t* const* u, uint32_t C, const uint64_t* pts, uint32_t R, uint64_t K, uint32_t S,
                  uint32_t Ll, uint32_t logN, const TowerConst* tq, uint64_t* out, void* scratch, hipStream_t s);
+// EvalLinearWSum with encrypted weights (wsum.hip): ciphertexts [k0, k0 + kc) of out [K][2][Ll][N], out[k] =
+// launch_dot's result on learner c's weight against its k-th update, summed over the C <= kWsumMaxLearners
+// learners; u[c] [K][2][Lu][N] with Lu >= Ll, its first Ll towers read in place; w[c] [K][2][Ll][N] (per_k) or
+// [1][2][Ll][N]; out overlapping none.  One launch chain: the summed-tensor pass and ONE key switch of the
+// chain's kc ciphertexts, scratch = ks_scratch_bytes(.., kc).
+constexpr int kWsumMaxLearners = 32;  // 2 x 32 base pointers by value in the kernel arguments
+void launch_wsum(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,
+                 const uint64_t* evk, const uint64_t* evk_sh, const uint64_t* const* u, uint32_t Lu,
+                 const uint64_t* const* w, bool per_k, uint32_t C, uint64_t k0, uint64_t kc, uint64_t* out,
+                 void* scratch, hipStream_t s);
 // Rotation (rotate.hip): out = (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)) under the rotation key of
 // the Galois element g; ct, out [K][2][Ll][N], not overlapping; scratch = ks_scratch_bytes(.., K).
 void launch_rotate(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,

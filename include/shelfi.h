@@ -444,6 +444,29 @@ size_t shelfi_gram_pairs(size_t C);
 /* slices S of the last successful shelfi_dev_gram on this context (a refused call leaves it unchanged; for
  * tests of the split) */
 uint64_t shelfi_gram_slice_count(const shelfi_ctx* ctx);
+/* cc->EvalLinearWSum with ENCRYPTED weights: sum_c w_c u_c over C learners' updates with weights the server
+ * cannot read (private dataset-size weights, encrypted selection or clipping factors, encrypted per-parameter
+ * masks), at one key switch per OUTPUT ciphertext instead of one per product.  Learner c has an update batch
+ * [K][2][u_towers][N] and a weight batch [Kw][2][towers][N], Kw = 1 (one weight ciphertext for its whole update)
+ * or Kw = K (one per update ciphertext).  For every k, per tower t < towers, in EVALUATION form, with w = w_{c,0}
+ * (Kw = 1) or w_{c,k} (Kw = K): c0 = sum_c w0 u_{c,k,0}, c1 = sum_c (w0 u_{c,k,1} + w1 u_{c,k,0}), c2 = sum_c w1
+ * u_{c,k,1} mod q_t, and out[k] = (c0, c1) + KeySwitch(c2) under the installed evaluation key.  out_dev
+ * [K][2][towers][N]: ordinary ciphertexts of depth 2 and scale = scale_w scale_u for shelfi_dev_rescale, _add and
+ * the decrypt calls.  out[k] is, bit for bit, shelfi_dev_dot of the C stacked weights against the C stacked k-th
+ * update ciphertexts, and at C = 1 shelfi_dev_mult of the weight with the update.  u_towers >= towers is part of the
+ * contract: weights that come out of a computation sit at a lower level than fresh updates, and the first `towers`
+ * towers of each update polynomial are read in place (polynomial stride u_towers N) -- towers [towers, u_towers) are
+ * never read, and the result is bit-equal to the call on contiguous prefix copies.  batches_dev, weights_dev: HOST
+ * arrays of C device pointers (the same batch may appear twice).  No evaluation key: SHELFI_ERR_STATE.  C outside
+ * 1..32 (larger cohorts go in groups through shelfi_dev_add), K = 0, Kw not 1 or K, towers outside 1..u_towers,
+ * u_towers > L, a NULL pointer (an array, an entry, out_dev), out_dev overlapping any update batch (over its stored
+ * u_towers extent) or any weight batch, and a chain with num_towers + special primes > 16: SHELFI_ERR_ARG; a refused
+ * call writes nothing.  The K outputs are cut into launch chains under SHELFI_EVAL_CHUNK_MIB, as shelfi_dev_mult's
+ * (shelfi_eval_chunk_count reports them; no output bit depends on them).  Uses the context's scratch (the key switch
+ * of a chain's ciphertexts) and synchronises `stream` before returning. */
+int shelfi_dev_wsum_ct(shelfi_ctx* ctx, const uint64_t* const* batches_dev, size_t C, size_t K, uint32_t u_towers,
+                       const uint64_t* const* weights_dev, size_t Kw, uint32_t towers, uint64_t* out_dev,
+                       void* stream);
 /* cc->EvalInnerProduct(ct, pt) (EvalMult(ct, pt) + EvalAddMany) for every pair of C ciphertext batches and R
  * plaintext batches, as one call: out_dev [C R][2][towers][N], entry c R + r, holds per tower, coefficient and
  * component i the canonical sum_k u_{c,k,i} p_{r,k} mod q_t -- the projection of learner c's update on the known
@@ -518,8 +541,8 @@ int shelfi_dev_rotate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_
 int shelfi_dev_eval_sum(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, uint32_t n,
                         uint64_t* out_dev, void* stream);
 /* The number of launch chains (chunks of the batch, each within the SHELFI_EVAL_CHUNK_MIB scratch budget,
- * 2048 by default) the last successful shelfi_dev_mult, shelfi_dev_gram, shelfi_dev_rescale, shelfi_dev_rotate or
- * shelfi_dev_eval_sum on this context took.  0 after a call that enqueued no chain (K = 0, index 0,
+ * 2048 by default) the last successful shelfi_dev_mult, shelfi_dev_gram, shelfi_dev_wsum_ct, shelfi_dev_rescale,
+ * shelfi_dev_rotate or shelfi_dev_eval_sum on this context took.  0 after a call that enqueued no chain (K = 0, index 0,
  * n = 1); a refused call leaves it unchanged.  For tests of the chunking. */
 uint64_t shelfi_eval_chunk_count(const shelfi_ctx* ctx);
 /* cc->EvalAdd(ct_a, ct_b) (mkhe.cpp:168, :368): out = a + b mod q_t over [K][2][towers][N]; out may be a
