@@ -38,6 +38,7 @@ def reload_switches() -> None:
     _lib.load().shelfi_reload_switches()
 
 _WIRE_CODES = {"shelfi": 0, "palisade": 1, "packed": 2, "seeded": 3}  # shelfi_set_wire_format's numbering
+_PACK_CODES = {"real": 0, "complex": 1}  # SHELFI_PACK_REAL, SHELFI_PACK_COMPLEX
 
 
 _PyBytes_FromStringAndSize = C.pythonapi.PyBytes_FromStringAndSize
@@ -95,12 +96,15 @@ class CKKS(Scheme):
     def __init__(self, scheme: str = "ckks", batchSize: int = 4096, scaleFactorBits: int = 52,
                  cryptodir: str = "../resources/cryptoparams/", *, multDepth: int = 1,
                  firstModBits: int = 60, ringDim: int = 0, device: int | None = None,
-                 seed: int = 0, decodeNoise: bool = True, wireFormat: str = "palisade"):
+                 seed: int = 0, decodeNoise: bool = True, wireFormat: str = "palisade",
+                 slotPacking: str = "real"):
         super().__init__(scheme)
         if scheme.lower() != "ckks":
             raise ValueError("only the 'ckks' scheme is implemented")
         if wireFormat not in _WIRE_CODES:
             raise ValueError("wireFormat must be 'palisade', 'shelfi', 'packed' or 'seeded'")
+        if slotPacking not in _PACK_CODES:
+            raise ValueError("slotPacking must be 'real' or 'complex'")
         self._wire = wireFormat
         self.batchSize = int(batchSize)
         self.scaleFactorBits = int(scaleFactorBits)
@@ -115,6 +119,8 @@ class CKKS(Scheme):
             check(self._lib.shelfi_set_seed(self._ctx, int(seed)))
         if not decodeNoise:
             self.set_decode_noise(False)
+        if slotPacking != "real":
+            self.set_slot_packing(slotPacking)
 
     # ------------------------------------------------------------ lifecycle --
     def __del__(self):
@@ -136,7 +142,10 @@ class CKKS(Scheme):
                 "device": inf.device, "moduli": [int(inf.moduli[i]) for i in range(L)],
                 "roots": [int(inf.roots[i]) for i in range(L)], "delta": inf.delta,
                 "key_id": int(inf.key_id), "keys_loaded": bool(inf.keys_loaded),
-                "palisade_keys": bool(inf.palisade_keys)}
+                "palisade_keys": bool(inf.palisade_keys),
+                "slot_packing": {v: k for k, v in _PACK_CODES.items()}[int(inf.slot_packing)],
+                # (0: a SHELFI_LIB_AB probe build from before the field, which packs one value a slot)
+                "values_per_ct": int(inf.values_per_ct) or int(inf.batch)}
 
     @property
     def ctx_handle(self) -> int:
@@ -165,6 +174,22 @@ class CKKS(Scheme):
             raise ValueError("wire format must be 'palisade', 'shelfi', 'packed' or 'seeded'")
         check(self._lib.shelfi_set_wire_format(self._ctx, _WIRE_CODES[fmt]), "set_wire_format")
         self._wire = fmt
+
+    def set_slot_packing(self, mode: str = "complex") -> None:
+        """What a slot holds.  "real" (the default): one value a slot, as the reference
+        encodes.  "complex": two -- slot s of ciphertext k holds x[k V + 2 s] + 1j * x[k V + 2 s + 1], so a
+        ciphertext carries V = 2 * batch values (info()["values_per_ct"]) and encrypt, decrypt and fuseDecrypt
+        (and device.encrypt / encode / decrypt ...) use ceil(n / V) ciphertexts for n values.  The weighted
+        average, the arena, the wire formats and the threshold chain run unchanged on such ciphertexts; a slot
+        product is a complex product (a norm is device.dot(u, device.conj(u))).  Decode noise flooding cannot run
+        on complex slots: decrypt raises RuntimeError until set_decode_noise(False) -- decodeNoise defaults to
+        True.  The mode is not recorded in a ciphertext; both ends must set it."""
+        if mode not in _PACK_CODES:
+            raise ValueError("slot packing must be 'real' or 'complex'")
+        check(self._lib.shelfi_set_slot_packing(self._ctx, _PACK_CODES[mode]), "set_slot_packing")
+
+    def slot_packing(self) -> str:
+        return {v: k for k, v in _PACK_CODES.items()}[int(self._lib.shelfi_get_slot_packing(self._ctx))]
 
     def wire_format(self) -> str:
         """The bytes format encrypt answers in right now."""
@@ -368,6 +393,24 @@ class CKKS(Scheme):
     def evalSumKeyGen(self) -> None:
         """cc->EvalSumKeyGen(sk): the rotation keys of indices 1, 2, 4, ..., batch / 2."""
         check(self._lib.shelfi_eval_sum_keygen(self._ctx), "evalSumKeyGen")
+
+    def conjugateKeyGen(self) -> None:
+        """The key of the automorphism X -> X^(2N - 1), which conjugates every slot (device.conj).  A rotation
+        key in all but its Galois element: one of the context's 64, listed by rotation_key_indices() as index
+        0, dropped with them by a key reload."""
+        check(self._lib.shelfi_conjugate_keygen(self._ctx), "conjugateKeyGen")
+
+    def get_conjugation_key(self) -> np.ndarray:
+        out = np.zeros(self._rotation_key_shape(), np.uint64)
+        check(self._lib.shelfi_get_conjugation_key(self._ctx, out.ctypes.data_as(_lib.u64p)), "get_conjugation_key")
+        return out
+
+    def set_conjugation_key(self, key: np.ndarray) -> None:
+        """Install a conjugation key made elsewhere (a keyless server is handed the learners' this way)."""
+        key = np.ascontiguousarray(key, np.uint64)
+        if key.shape != self._rotation_key_shape():
+            raise ValueError("conjugation key must have shape %r" % (self._rotation_key_shape(),))
+        check(self._lib.shelfi_set_conjugation_key(self._ctx, key.ctypes.data_as(_lib.u64p)), "set_conjugation_key")
 
     def rotation_key_indices(self) -> List[int]:
         """The rotation indices whose keys this context holds."""

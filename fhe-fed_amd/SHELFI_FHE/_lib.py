@@ -46,6 +46,8 @@ class Info(C.Structure):
         ("key_id", C.c_uint64),
         ("keys_loaded", C.c_int32),
         ("palisade_keys", C.c_int32),
+        ("slot_packing", C.c_uint32),
+        ("values_per_ct", C.c_uint32),
     ]
 
 
@@ -95,6 +97,8 @@ SIGNATURES = {
     "shelfi_encrypt": (C.c_int, [C.c_void_p, f64p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_size_t)]),
     "shelfi_set_wire_format": (C.c_int, [C.c_void_p, C.c_int]),
     "shelfi_get_wire_format": (C.c_int, [C.c_void_p]),
+    "shelfi_set_slot_packing": (C.c_int, [C.c_void_p, C.c_int]),
+    "shelfi_get_slot_packing": (C.c_int, [C.c_void_p]),
     "shelfi_palisade_parse": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(PalisadeInfo), u64p]),
     "shelfi_palisade_write": (C.c_int, [C.c_void_p, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint32, u64p,
                                         C.c_uint64, u64p, C.c_uint64, C.c_uint64, C.c_double, C.c_int,
@@ -209,6 +213,10 @@ SIGNATURES = {
                                     C.c_void_p]),
     "shelfi_dev_eval_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
                                       C.c_void_p]),
+    "shelfi_conjugate_keygen": (C.c_int, [C.c_void_p]),
+    "shelfi_get_conjugation_key": (C.c_int, [C.c_void_p, u64p]),
+    "shelfi_set_conjugation_key": (C.c_int, [C.c_void_p, u64p]),
+    "shelfi_dev_conjugate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "shelfi_eval_chunk_count": (C.c_uint64, [C.c_void_p]),
     "shelfi_dev_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                  C.c_void_p]),

@@ -372,12 +372,14 @@ def modq(ckks, buf):
 
 
 def encrypt(ckks, x, out=None):
-    """encode + encrypt a float64 CUDA vector into ceil(n / batch) ciphertexts."""
+    """encode + encrypt a float64 CUDA vector into ceil(n / V) ciphertexts, V = info()["values_per_ct"]: batch,
+    or 2 * batch under complex slot packing (CKKS.set_slot_packing; x is then the float64 view of a complex128
+    vector)."""
     torch = _torch()
     if not x.is_cuda or x.dtype != torch.float64:
         raise ValueError("x must be a float64 CUDA tensor")
     x = x.contiguous().view(-1)
-    B = ckks.info()["batch"]
+    B = ckks.info()["values_per_ct"]
     K = (x.numel() + B - 1) // B
     if out is None:
         out = empty_ct(ckks, K, x.device)
@@ -678,6 +680,18 @@ def rotate(ckks, ct, r: int, out=None):
     return out
 
 
+def conj(ckks, ct, out=None):
+    """The complex conjugate of every slot of K ciphertexts of any level: the automorphism X -> X^(2N - 1) and
+    its key switch, (sigma(c0) + u0, u1) with (u0, u1) = KeySwitch(sigma(c1)).  Needs ckks.conjugateKeyGen().
+    out must not overlap ct.  Scale unchanged.  Under complex slot packing dot(u, conj(u)) is the squared norm,
+    and (ct + conj(ct)) / 2 holds the even-indexed values alone."""
+    _check_ct(ct, ckks, any_level=True)
+    out = _like(ckks, ct, out)
+    check(_lib.load().shelfi_dev_conjugate(ckks._ctx, C.c_void_p(ct.data_ptr()), ct.shape[0], int(ct.shape[2]),
+                                           C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(ct))), "dev_conjugate")
+    return out
+
+
 def eval_sum(ckks, ct, n: int, out=None):
     """cc->EvalSum(ct, n), n a power of two in 1..batch: slot i of the result holds
     sum_{j < n} x[(i + j) mod batch], by log2(n) rotate-and-add steps (needs the keys of indices
@@ -740,7 +754,7 @@ def encode(ckks, x, towers=None, scale=None, out=None):
     if not x.is_cuda or x.dtype != torch.float64 or not x.is_contiguous():
         raise ValueError("x must be a contiguous float64 CUDA tensor")
     inf = ckks.info()
-    L, N, B = inf["num_towers"], inf["ring_dim"], inf["batch"]
+    L, N, B = inf["num_towers"], inf["ring_dim"], inf["values_per_ct"]
     towers = L if towers is None else int(towers)
     scale = float(inf["delta"] if scale is None else scale)
     if not 0 <= towers < 1 << 32:
@@ -853,7 +867,8 @@ def dot_plain(ckks, ct, pt, out=None):
 
 def _one_hots(ckks, l: int, P: int, device):
     """The P one-hot slot vectors e_p as plaintexts [P][l][N] at scale q[l - 1], cached on the context per
-    (l, P, device) and parameter generation."""
+    (l, P, device) and parameter generation.  The same plaintexts in either slot packing: vector p spans the V
+    values of one plaintext and its 1.0 is the real part of slot p (value p, or 2 p under complex packing)."""
     torch = _torch()
     gen = getattr(ckks, "_params_gen", 0)
     cache = getattr(ckks, "_dev_one_hots", None)
@@ -862,9 +877,9 @@ def _one_hots(ckks, l: int, P: int, device):
     key = (int(l), int(P), str(device))
     if key not in cache[1]:
         inf = ckks.info()
-        B = inf["batch"]
-        x = torch.zeros(P * B, dtype=torch.float64, device=device)
-        x[torch.arange(P, device=device) * (B + 1)] = 1.0
+        V = inf["values_per_ct"]
+        x = torch.zeros(P * V, dtype=torch.float64, device=device)
+        x[torch.arange(P, device=device) * (V + V // inf["batch"])] = 1.0
         cache[1][key] = encode(ckks, x, towers=l, scale=float(inf["moduli"][l - 1]))
     return cache[1][key]
 
@@ -909,7 +924,7 @@ def encrypt_seeded(ckks, x):
         raise ValueError("x must be a float64 CUDA tensor")
     x = x.contiguous().view(-1)
     inf = ckks.info()
-    K = (x.numel() + inf["batch"] - 1) // inf["batch"]
+    K = (x.numel() + inf["values_per_ct"] - 1) // inf["values_per_ct"]
     c0 = torch.empty((K, inf["num_towers"], inf["ring_dim"]), dtype=torch.int64, device=x.device)
     seed = (C.c_uint8 * 32)()
     check(_lib.load().shelfi_dev_encrypt_seeded(ckks._ctx, C.c_void_p(x.data_ptr()), x.numel(),

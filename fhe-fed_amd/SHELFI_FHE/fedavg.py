@@ -123,10 +123,16 @@ def top_k_mask(sensitivity: np.ndarray, fraction: float) -> np.ndarray:
 class SecureFedAvg:
     """One encrypted FedAvg round (benchmark.py:447-543) through a SHELFI_FHE.CKKS."""
 
-    def __init__(self, ckks, selection: Optional[Selection] = None, pack: bool = False):
+    def __init__(self, ckks, selection: Optional[Selection] = None, pack: bool = False,
+                 slot_packing: Optional[str] = None):
+        """slot_packing: "real" or "complex" is passed through to ckks.set_slot_packing (two values a slot
+        halve the ciphertexts of every key; the context must then have its decode noise off); None leaves
+        the context's mode as it is."""
         self.ckks = ckks
         self.sel = selection or Selection("all")
         self.pack = pack
+        if slot_packing is not None:
+            ckks.set_slot_packing(slot_packing)
         self.times = {}
 
     def run(self, client_states: Sequence, weights: Optional[Sequence[float]] = None):

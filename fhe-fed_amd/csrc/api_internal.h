@@ -200,6 +200,13 @@ bool gen_flag_raised(const shelfi_ctx* ctx, const GenFlag& f, int w);
 bool encode_needs_approx(const shelfi_ctx* ctx, const GenFlag& f);
 
 DecodeNoise decode_noise_begin(shelfi_ctx* ctx, uint64_t K, const GenFlag& fl);
+// complex slot packing with decode noise enabled: SHELFI_ERR_STATE (decode_noise_begin checks it too)
+void require_no_flood_on_complex(const shelfi_ctx* ctx);
+// complex slot packing reads / writes a device vector as 16-byte (re, im) words
+inline void require_pair_aligned(const shelfi_ctx* ctx, const void* v) {
+  if (ctx->p.pack && (reinterpret_cast<uintptr_t>(v) & 15))
+    throw Error{SHELFI_ERR_ARG, "complex slot packing needs a 16-byte aligned value vector"};
+}
 void decode_noise_readback(shelfi_ctx* ctx, const DecodeNoise& dn);
 void decode_noise_end(shelfi_ctx* ctx, const DecodeNoise& dn);
 

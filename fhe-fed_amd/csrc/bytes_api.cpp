@@ -68,7 +68,7 @@ static void encrypt_bytes_pipeline(shelfi_ctx* ctx, const double* x, size_t n, u
   const size_t ct_bytes = 2ull * p.L * p.N * 8;
   uint64_t kc = std::max<uint64_t>(1, (64ull << 20) / ct_bytes);
   kc = std::min<uint64_t>(kc, K);
-  const size_t xin = kc * p.batch * 8, cto = kc * ct_bytes;
+  const size_t xin = kc * values_per_ct(p) * 8, cto = kc * ct_bytes;
   // packed wire output: the chunk is packed on the device (U_t bits per residue) before its D2H
   // seeded wire output: the symmetric encrypt's c0 [kc][L][N] takes the chunk's uint64 buffer and is packed
   // one group a ciphertext
@@ -88,7 +88,7 @@ static void encrypt_bytes_pipeline(shelfi_ctx* ctx, const double* x, size_t n, u
   for (uint64_t ci = 0; ci < nchunks; ++ci) {
     const int b = (int)(ci & 1);
     const uint64_t k0 = ci * kc, kn = std::min<uint64_t>(kc, K - k0);
-    const uint64_t xs = k0 * p.batch, xn = std::min<uint64_t>(n - xs, kn * p.batch);
+    const uint64_t xs = k0 * values_per_ct(p), xn = std::min<uint64_t>(n - xs, kn * values_per_ct(p));
     if (ci >= 2) SHELFI_HIP(hipStreamWaitEvent(pp.a, pp.computed[b], 0));  // x buffer consumed
     sr.s.h2d(xb[b], x + xs, xn * 8, pp.a);
     SHELFI_HIP(hipEventRecord(pp.in_ready[b], pp.a));
@@ -458,7 +458,7 @@ int shelfi_encrypt_into(shelfi_ctx* ctx, const double* x, size_t n, uint8_t* out
     if (ctx->wire == 3) require_own_secret(ctx);
     DeviceGuard g(ctx->device);
     const Params& p = ctx->p;
-    const uint64_t K = (n + p.batch - 1) / p.batch;  // ckks.cpp:65
+    const uint64_t K = (n + values_per_ct(p) - 1) / values_per_ct(p);  // ckks.cpp:65
     size_t total = 0;
     make_output(ctx, ctx->wire, K, 1, 0, p.delta, nullptr, &total);
     *out_len = total;
@@ -559,12 +559,13 @@ int shelfi_decrypt(shelfi_ctx* ctx, const uint8_t* blob, size_t len, size_t n, d
     require_keys(ctx);
     DeviceGuard g(ctx->device);
     const Params& p = ctx->p;
+    require_no_flood_on_complex(ctx);
     const CtLayout h = open_cts(ctx, blob, len);
-    if (n > h.K * (uint64_t)p.batch)
+    if (n > h.K * values_per_ct(p))
       throw Error{SHELFI_ERR_ARG, "decrypt: data_dimensions exceeds the slots in the ciphertexts"};
     if (!n) return;
     // ckks.cpp:192-196: ciphertext i contributes min(batch, n - i*batch) values
-    const uint64_t K = (n + p.batch - 1) / p.batch;
+    const uint64_t K = (n + values_per_ct(p) - 1) / values_per_ct(p);
     advise_huge(out, n * 8);
     const GenFlag fl = next_gen_flag(ctx);
     DecodeNoise dn = decode_noise_begin(ctx, K, fl);
@@ -578,7 +579,7 @@ int shelfi_decrypt(shelfi_ctx* ctx, const uint8_t* blob, size_t len, size_t n, d
       const size_t ct_bytes = 2ull * pd.L * p.N * 8;  // only the decode's towers travel
       uint64_t kc = std::max<uint64_t>(1, (64ull << 20) / ct_bytes);
       kc = std::min<uint64_t>(kc, K);
-      const size_t cin = kc * ct_bytes, dout = kc * p.batch * 8;
+      const size_t cin = kc * ct_bytes, dout = kc * values_per_ct(p) * 8;
       // a packed blob's tower prefix lands packed and is unpacked on the device
       // (a seeded blob's c0 prefix lands the same way, and c1's prefix is expanded beside it)
       const bool hp = h.packed || h.seeded;
@@ -599,7 +600,7 @@ int shelfi_decrypt(shelfi_ctx* ctx, const uint8_t* blob, size_t len, size_t n, d
       for (uint64_t ci = 0; ci < nchunks; ++ci) {
         const int b = (int)(ci & 1);
         const uint64_t k0 = ci * kc, kn = std::min<uint64_t>(kc, K - k0);
-        const uint64_t o0 = k0 * p.batch, on = std::min<uint64_t>(n - o0, kn * p.batch);
+        const uint64_t o0 = k0 * values_per_ct(p), on = std::min<uint64_t>(n - o0, kn * values_per_ct(p));
         if (ci >= 2) SHELFI_HIP(hipStreamWaitEvent(pp.a, pp.computed[b], 0));
         h.pieces(k0, kn, p, pcs, pd.L);
         sr.s.h2dv(hp ? pb[b] : cb[b], pcs.data(), pcs.size(), pp.a);
@@ -690,6 +691,7 @@ int shelfi_fuse_decrypt(shelfi_ctx* ctx, const uint8_t* const* partials, const s
   std::lock_guard<std::mutex> lk(ctx->mu);
   return guarded([&] {
     const Params& p = ctx->p;
+    require_no_flood_on_complex(ctx);
     std::vector<BlobHeader> hs(P);
     size_t leads = 0;
     for (size_t i = 0; i < P; ++i) {
@@ -702,14 +704,14 @@ int shelfi_fuse_decrypt(shelfi_ctx* ctx, const uint8_t* const* partials, const s
     if (leads != 1) throw Error{SHELFI_ERR_FORMAT, "fuseDecrypt: exactly one partial decryption must be the lead's"};
     if (hs[0].batch != p.batch) throw Error{SHELFI_ERR_FORMAT, "fuseDecrypt: batch size differs from the context's"};
     const uint64_t K = hs[0].K;
-    if (n > K * (uint64_t)p.batch)
+    if (n > K * values_per_ct(p))
       throw Error{SHELFI_ERR_ARG, "fuseDecrypt: data_dimensions exceeds the slots in the ciphertexts"};
     if (!n) return;
     DeviceGuard g(ctx->device);
-    const uint64_t Kn = (n + p.batch - 1) / p.batch;
+    const uint64_t Kn = (n + values_per_ct(p) - 1) / values_per_ct(p);
     const size_t poly_bytes = (size_t)p.L * p.N * 8;
     const uint64_t kc = std::min<uint64_t>(Kn, std::max<uint64_t>(1, (64ull << 20) / (P * poly_bytes)));
-    const size_t pin = kc * poly_bytes, dout = kc * p.batch * 8;
+    const size_t pin = kc * poly_bytes, dout = kc * values_per_ct(p) * 8;
     uint8_t* io = (uint8_t*)ensure(ctx->io, ctx->io_bytes, P * pin + dout);
     double* ob = (double*)(io + P * pin);
     hipStream_t s = ctx->stream;
@@ -718,7 +720,7 @@ int shelfi_fuse_decrypt(shelfi_ctx* ctx, const uint8_t* const* partials, const s
     int log_error = -1;
     for (uint64_t k0 = 0; k0 < Kn; k0 += kc) {
       const uint64_t kn = std::min<uint64_t>(kc, Kn - k0);
-      const uint64_t o0 = k0 * p.batch, on = std::min<uint64_t>(n - o0, kn * p.batch);
+      const uint64_t o0 = k0 * values_per_ct(p), on = std::min<uint64_t>(n - o0, kn * values_per_ct(p));
       FuseIn fz{};
       fz.P = (uint32_t)P;
       for (size_t i = 0; i < P; ++i) {

@@ -99,8 +99,19 @@ bool encode_needs_approx(const shelfi_ctx* ctx, const GenFlag& f) {
 
 // Noise-flooding setup for one decrypt of K ciphertexts (enabled by
 // shelfi_set_decode_noise); its randomness comes from the ctx stream like encrypt's.
+// Complex slot packing has no flooded decode: PALISADE's flooding estimates sigma from the imaginary parts,
+// which then carry data.  Refused before anything is enqueued, never decoded without the
+// noise the caller asked for.
+void require_no_flood_on_complex(const shelfi_ctx* ctx) {
+  if (ctx->p.pack && ctx->decode_noise)
+    throw Error{SHELFI_ERR_STATE,
+                "decode noise flooding cannot run on complex slot packing: call set_decode_noise(False) "
+                "(shelfi_set_decode_noise(ctx, 0, 1.0)) before decrypting; threshold smudging is unaffected"};
+}
+
 DecodeNoise decode_noise_begin(shelfi_ctx* ctx, uint64_t K, const GenFlag& fl) {
   DecodeNoise dn;
+  require_no_flood_on_complex(ctx);
   if (!ctx->decode_noise) return dn;
   dn.fail = fl;
   dn.enabled = 1;
@@ -167,6 +178,23 @@ int shelfi_set_decode_noise(shelfi_ctx* ctx, int enabled, double m_factor) {
   ctx->decode_noise = enabled ? 1 : 0;
   ctx->decode_m_factor = m_factor;
   return SHELFI_OK;
+}
+
+int shelfi_set_slot_packing(shelfi_ctx* ctx, int mode) {
+  if (!ctx) return SHELFI_ERR_ARG;
+  if (mode != SHELFI_PACK_REAL && mode != SHELFI_PACK_COMPLEX) {
+    set_error("slot packing: SHELFI_PACK_REAL (0) or SHELFI_PACK_COMPLEX (1)");
+    return SHELFI_ERR_ARG;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  ctx->p.pack = (uint32_t)mode;
+  return SHELFI_OK;
+}
+
+int shelfi_get_slot_packing(const shelfi_ctx* ctx) {
+  if (!ctx) return -1;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return (int)ctx->p.pack;
 }
 
 int shelfi_set_decode_exact(shelfi_ctx* ctx, int exact) {

@@ -431,6 +431,7 @@ static void set_params(shelfi_ctx* ctx, uint32_t N, uint32_t L, uint32_t scale_b
   }
   // EXACTRESCALE level-0 scaling factor = (double)q_{L-1} (CT1.txt@265059).
   p.delta = (double)q[L - 1];
+  p.pack = ctx->p.pack;  // context state (shelfi_set_slot_packing), kept across a parameter reload
   ctx->p = p;
   build_tables(ctx);
 }
@@ -698,6 +699,8 @@ int shelfi_ctx_info(const shelfi_ctx* ctx, shelfi_info* o) {
   o->key_id = ctx->key_id;
   o->keys_loaded = ctx->keys_loaded ? 1 : 0;
   o->palisade_keys = ctx->palisade_keys ? 1 : 0;
+  o->slot_packing = ctx->p.pack;
+  o->values_per_ct = (uint32_t)values_per_ct(ctx->p);
   return SHELFI_OK;
 }
 

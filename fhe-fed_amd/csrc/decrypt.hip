@@ -851,11 +851,29 @@ __device__ __forceinline__ double flood_nsd(const FloodArgs& fa, uint64_t k, uin
 // stages follow on register columns (fft_fwd_cols).  A single pass writes the real parts
 // of the first `n` slots straight into the caller's output vector; FLOOD adds the decode
 // noise there, in the output domain (as fft_fwd_cols).
-template <bool FLOOD>
-__global__ __launch_bounds__(256) void fft_fwd_blocks(double2* __restrict__ buf, uint32_t logS,
-                                                      uint32_t blkLog, const double2* __restrict__ tw,
-                                                      double* __restrict__ out, uint64_t n,
-                                                      int final_pass, FloodArgs fa) {
+// Decoded slot gi into the call's n output values.  Real packing: its real part at out[gi].  Complex packing
+// (CX): (re, im) at out[2 gi], out[2 gi + 1] as one aligned 16-byte word, under the same
+// n-tail rule (the pair whose first value is out[n - 1] stores only that).
+template <bool CX>
+__device__ __forceinline__ void dec_slot(double* __restrict__ out, uint64_t n, uint64_t gi, double2 v) {
+  if constexpr (CX) {
+    if (2 * gi + 1 < n)
+      reinterpret_cast<double2*>(out)[gi] = v;
+    else if (2 * gi < n)
+      out[2 * gi] = v.x;
+  } else {
+    if (gi < n) out[gi] = v.x;
+  }
+}
+
+// (fft_fwd_blocks and fft_fwd_whole are bodies shared by a real and a both-parts (_cx) entry point, so the
+// real forms keep their names and their code; FLOOD and STATS have no complex form)
+template <bool FLOOD, bool CX>
+__device__ __forceinline__ void fft_fwd_blocks_body(double2* __restrict__ buf, uint32_t logS,
+                                                    uint32_t blkLog, const double2* __restrict__ tw,
+                                                    double* __restrict__ out, uint64_t n,
+                                                    int final_pass, FloodArgs fa) {
+  static_assert(!(FLOOD && CX), "flooding estimates sigma from the imaginary parts");
   extern __shared__ __attribute__((aligned(16))) double2 smc[];
   const uint32_t S = 1u << logS, blk = 1u << blkLog;
   const uint32_t sh = logS - blkLog;
@@ -886,6 +904,10 @@ __global__ __launch_bounds__(256) void fft_fwd_blocks(double2* __restrict__ buf,
     }
     for (uint32_t i = threadIdx.x; i < blk; i += 256) {
       const uint64_t gi = off + i;
+      if constexpr (CX) {
+        dec_slot<true>(out, n, gi, smc[i]);
+        continue;
+      }
       double v = smc[i].x;
       if (FLOOD) {  // fft_fwd_cols's output-domain stream: normal (i div S/16) of block (i mod S/16)
         const uint32_t S16 = S >> 4, nidx = i / S16;
@@ -900,6 +922,19 @@ __global__ __launch_bounds__(256) void fft_fwd_blocks(double2* __restrict__ buf,
   } else {
     for (uint32_t i = threadIdx.x; i < blk; i += 256) buf[off + i] = smc[i];
   }
+}
+template <bool FLOOD>
+__global__ __launch_bounds__(256) void fft_fwd_blocks(double2* __restrict__ buf, uint32_t logS,
+                                                      uint32_t blkLog, const double2* __restrict__ tw,
+                                                      double* __restrict__ out, uint64_t n,
+                                                      int final_pass, FloodArgs fa) {
+  fft_fwd_blocks_body<FLOOD, false>(buf, logS, blkLog, tw, out, n, final_pass, fa);
+}
+__global__ __launch_bounds__(256) void fft_fwd_blocks_cx(double2* __restrict__ buf, uint32_t logS,
+                                                         uint32_t blkLog, const double2* __restrict__ tw,
+                                                         double* __restrict__ out, uint64_t n,
+                                                         int final_pass, FloodArgs fa) {
+  fft_fwd_blocks_body<false, true>(buf, logS, blkLog, tw, out, n, final_pass, fa);
 }
 
 // FFTSpecial's first pass (decode, not the final pass): block b of ciphertext k, DIT half-sizes
@@ -1002,6 +1037,51 @@ __global__ __launch_bounds__(256) void fft_fwd_cols(const double2* __restrict__ 
   }
 }
 
+// fft_fwd_cols<LOGR, false> for complex slot packing: both parts of every slot (dec_slot).  A kernel of its own
+// (a shared body moved the flooded forms' register counts): the last stage, whose 2^LOGR outputs are all live
+// here where the real form keeps only their real parts, stores each pair as it is done (as fft_fwd_whole), so
+// the column holds its occupancy (register counts in DESIGN.md §2.19).
+template <int LOGR>
+__global__ __launch_bounds__(256) void fft_fwd_cols_cx(const double2* __restrict__ buf, uint32_t logS,
+                                                       const double2* __restrict__ tw,
+                                                       double* __restrict__ out, uint64_t n) {
+  constexpr int R = 1 << LOGR;
+  const uint32_t S = 1u << logS;
+  const uint32_t BLK = S >> LOGR;
+  const uint32_t bpp = BLK / 256;
+  const uint64_t k = blockIdx.x / bpp;
+  const uint32_t col = (blockIdx.x % bpp) * 256 + threadIdx.x;
+  double2 v[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) v[r] = buf[k * S + col + (uint64_t)r * BLK];
+#pragma unroll
+  for (int s = 0; s < LOGR - 1; ++s) {
+    const uint32_t lenh = BLK << s;
+    const int tr = 1 << s;
+#pragma unroll
+    for (int r0 = 0; r0 < R; ++r0) {
+      if ((r0 >> s) & 1) continue;
+      const int r1 = r0 + tr;
+      const uint32_t j = col + (uint32_t)(r0 & ((2 << s) - 1)) * BLK;  // (col + r0 BLK) mod len
+      const double2 W = tw[lenh + j];
+      const double2 u = v[r0];
+      const double2 w = cmul(v[r1], W);
+      v[r0] = cadd(u, w);
+      v[r1] = csub(u, w);
+    }
+  }
+#pragma unroll
+  for (int r0 = 0; r0 < R / 2; ++r0) {  // the last stage: half-size S/2, rows r0 and r0 + R/2
+    asm volatile("" ::: "memory");  // each pair's twiddle load and stores stay with the pair
+    const int r1 = r0 + R / 2;
+    const double2 W = tw[(S >> 1) + col + (uint32_t)r0 * BLK];
+    const double2 w = cmul(v[r1], W);
+    const uint64_t gi = k * S + col + (uint64_t)r0 * BLK;
+    dec_slot<true>(out, n, gi, cadd(v[r0], w));
+    dec_slot<true>(out, n, gi + (S >> 1), csub(v[r0], w));
+  }
+}
+
 // decode_stats_kernel's sums inside the whole-vector decode (round 5): a[i] holds FFT-input position
 // P = 1024 w + 4 (l + 64 (i >> 2)) + (i & 3); pair (P, P ^ (2^h - 1)) (h = P's leading bit, P in the
 // lower half of its octave) contributes a = x.re + y.im and b = x.im + y.re, positions 0 and 1 their
@@ -1059,10 +1139,11 @@ __device__ __forceinline__ double2 fft_whole_flood_stats(const double2 (&a)[16],
 // workgroup also sums decode_stats_kernel's statistics of its vector (fft_whole_flood_stats) into
 // part[k]; flood_add_kernel then adds the noise to out (adding it here, beside the 16 values per thread,
 // spilled under the 128-VGPR cap and ran slower than the extra pass).
-template <bool STATS>
-__global__ __launch_bounds__(1024) void fft_fwd_whole(const double2* __restrict__ buf, const double2* __restrict__ tw,
-                                                      double* __restrict__ out, uint64_t n,
-                                                      double2* __restrict__ part) {
+template <bool STATS, bool CX>
+__device__ __forceinline__ void fft_fwd_whole_body(const double2* __restrict__ buf, const double2* __restrict__ tw,
+                                                   double* __restrict__ out, uint64_t n,
+                                                   double2* __restrict__ part) {
+  static_assert(!(STATS && CX), "flooding estimates sigma from the imaginary parts");
   constexpr uint32_t S = 1u << kFftWholeLogS, BLK = 1024;
   constexpr int R = 16;
   __shared__ double lds[16 * kFftWholeRow];
@@ -1115,18 +1196,37 @@ __global__ __launch_bounds__(1024) void fft_fwd_whole(const double2* __restrict_
     }
   }
   // uniform base + 32-bit offsets (16 precomputed 64-bit addresses would not fit)
-  double* __restrict__ ok = out + k * S;
-  const uint32_t rem = n > k * S ? (uint32_t)std::min<uint64_t>(n - k * S, S) : 0u;
+  // (CX: the vector's 2 S values, both parts of each pair of the last stage)
+  constexpr uint32_t VS = CX ? 2 * S : S;
+  double* __restrict__ ok = out + k * VS;
+  const uint32_t rem = n > k * VS ? (uint32_t)std::min<uint64_t>(n - k * VS, VS) : 0u;
 #pragma unroll
   for (int r0 = 0; r0 < R / 2; ++r0) {
     asm volatile("" ::: "memory");
     const int r1 = r0 + R / 2;
     const double2 W = tw[(BLK << 3) + T + (uint32_t)r0 * BLK];
-    const double vx = __dsub_rn(__dmul_rn(a[r1].x, W.x), __dmul_rn(a[r1].y, W.y));  // cmul(a[r1], W).x
     const uint32_t i0 = T + (uint32_t)r0 * BLK, i1 = T + (uint32_t)r1 * BLK;
-    if (i0 < rem) ok[i0] = __dadd_rn(a[r0].x, vx);
-    if (i1 < rem) ok[i1] = __dsub_rn(a[r0].x, vx);
+    if constexpr (CX) {
+      const double2 v = cmul(a[r1], W);
+      dec_slot<true>(ok, rem, i0, cadd(a[r0], v));
+      dec_slot<true>(ok, rem, i1, csub(a[r0], v));
+    } else {
+      const double vx = __dsub_rn(__dmul_rn(a[r1].x, W.x), __dmul_rn(a[r1].y, W.y));  // cmul(a[r1], W).x
+      if (i0 < rem) ok[i0] = __dadd_rn(a[r0].x, vx);
+      if (i1 < rem) ok[i1] = __dsub_rn(a[r0].x, vx);
+    }
   }
+}
+template <bool STATS>
+__global__ __launch_bounds__(1024) void fft_fwd_whole(const double2* __restrict__ buf, const double2* __restrict__ tw,
+                                                      double* __restrict__ out, uint64_t n,
+                                                      double2* __restrict__ part) {
+  fft_fwd_whole_body<STATS, false>(buf, tw, out, n, part);
+}
+__global__ __launch_bounds__(1024) void fft_fwd_whole_cx(const double2* __restrict__ buf, const double2* __restrict__ tw,
+                                                         double* __restrict__ out, uint64_t n,
+                                                         double2* __restrict__ part) {
+  fft_fwd_whole_body<false, true>(buf, tw, out, n, part);
 }
 
 // The decode noise of a flooded whole-vector decode, added to the decoded outputs (fft_fwd_cols<LOGR,
@@ -1177,6 +1277,9 @@ void launch_decrypt(const Params& p, const DeviceTables& dt, const DeviceKeys& d
                     void* scratch, hipStream_t s, const DecodeNoise* dn, bool sum_in, uint32_t ct_L,
                     GenFlag crt_flag, bool exact, const FuseIn* fuse_in) {
   if (!K) return;
+  const bool cx = p.pack != 0;  // both parts of every slot: the final writers' _cx forms
+  if (cx && dn && dn->enabled)
+    throw Error{SHELFI_ERR_STATE, "decrypt: decode noise flooding cannot run on complex slots"};
   if (!ct_L) ct_L = p.L;
   if (ct_L < p.L) throw Error{SHELFI_ERR_ARG, "decrypt: fewer ciphertext towers than decoded towers"};
   exact = exact || dt.crt_nc == 0;  // towers too wide for crt_value's columns: always exact
@@ -1320,8 +1423,8 @@ void launch_decrypt(const Params& p, const DeviceTables& dt, const DeviceKeys& d
       const uint64_t th = K * (p.batch >> 4);
       hipLaunchKernelGGL(flood_add_kernel, dim3((uint32_t)((th + 255) / 256)), dim3(256), 0, s, out, n, logS, K, fa);
     } else {
-      hipLaunchKernelGGL(fft_fwd_whole<false>, dim3((uint32_t)K), dim3(1024), 0, s, fbuf, dt.fft_fwd, out, n,
-                         (double2*)nullptr);
+      hipLaunchKernelGGL(cx ? fft_fwd_whole_cx : fft_fwd_whole<false>, dim3((uint32_t)K), dim3(1024), 0, s, fbuf,
+                         dt.fft_fwd, out, n, (double2*)nullptr);
     }
     SHELFI_HIP(hipGetLastError());
     return;
@@ -1336,15 +1439,17 @@ void launch_decrypt(const Params& p, const DeviceTables& dt, const DeviceKeys& d
   else if (fused_flood && flogR == 0)
     hipLaunchKernelGGL(fft_fwd_blocks<true>, fg, dim3(256), lds, s, fbuf, logS, fblkLog, dt.fft_fwd, out, n, 1, fa);
   else
-    hipLaunchKernelGGL(fft_fwd_blocks<false>, fg, dim3(256), lds, s, fbuf, logS,
+    hipLaunchKernelGGL(cx ? fft_fwd_blocks_cx : fft_fwd_blocks<false>, fg, dim3(256), lds, s, fbuf, logS,
                        fblkLog, dt.fft_fwd, out, n, flogR == 0 ? 1 : 0, fa);
   SHELFI_HIP(hipGetLastError());
   if (flogR > 0) {
     const uint64_t nb = K * ((p.batch >> flogR) / 256);
 #define COLS_FWD1(LR, FL) \
   hipLaunchKernelGGL((fft_fwd_cols<LR, FL>), dim3((uint32_t)nb), dim3(256), 0, s, fbuf, logS, dt.fft_fwd, out, n, fa)
-#define COLS_FWD(LR)                     \
-  if (fused_flood) COLS_FWD1(LR, true);  \
+#define COLS_FWD(LR)                                                                                                   \
+  if (cx)                                                                                                              \
+    hipLaunchKernelGGL(fft_fwd_cols_cx<LR>, dim3((uint32_t)nb), dim3(256), 0, s, fbuf, logS, dt.fft_fwd, out, n);     \
+  else if (fused_flood) COLS_FWD1(LR, true);                                                                           \
   else COLS_FWD1(LR, false);
     switch (flogR) {
       case 1: COLS_FWD(1) break;

@@ -22,8 +22,10 @@ namespace shelfi {
 void dev_decrypt_locked(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, double scale, size_t n,
                         double* out_dev, hipStream_t s, bool sum_in, const FuseIn* fuse) {
   require_towers(ctx->p, towers);
-  if (n > (uint64_t)K * ctx->p.batch) throw Error{SHELFI_ERR_ARG, "n exceeds the slots in K ciphertexts"};
-  const uint64_t Kn = (n + ctx->p.batch - 1) / ctx->p.batch;
+  require_no_flood_on_complex(ctx);
+  require_pair_aligned(ctx, out_dev);
+  if (n > (uint64_t)K * values_per_ct(ctx->p)) throw Error{SHELFI_ERR_ARG, "n exceeds the slots in K ciphertexts"};
+  const uint64_t Kn = (n + values_per_ct(ctx->p) - 1) / values_per_ct(ctx->p);
   if (!Kn) return;
   const size_t ct_words = 2ull * towers * ctx->p.N, part_words = (size_t)towers * ctx->p.N;
   const GenFlag fl = next_gen_flag(ctx);
@@ -38,7 +40,7 @@ void dev_decrypt_locked(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint3
     dn.reset = 1;
     const auto bytes_of = [&](uint64_t kc) { return decrypt_scratch_bytes(p, kc); };
     for_chunks(ctx, Kn, switches().dev_chunk_mib, bytes_of, [&](uint64_t k0, uint64_t kc, void* scratch) {
-      const uint64_t o0 = k0 * p.batch, on = std::min<uint64_t>(n - o0, kc * p.batch);
+      const uint64_t o0 = k0 * values_per_ct(p), on = std::min<uint64_t>(n - o0, kc * values_per_ct(p));
       dn.g0 = g0 + k0;
       if (fuse) {
         FuseIn fz = *fuse;
@@ -141,6 +143,29 @@ int dev_ct_op(CtOp op, shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b
                                                      (hipStream_t)stream);
   });
 }
+
+// Rotate's and Conjugate's call behind the key lookup: sigma_g and its key switch over K ciphertexts in launch
+// chains under SHELFI_EVAL_CHUNK_MIB.  ctx lock held, device set.
+void dev_galois_chains(shelfi_ctx* ctx, LevelState& l, const EvalState::RotKey& rk, uint32_t g, const uint64_t* ct_dev,
+                       size_t K, uint32_t towers, uint64_t* out_dev, hipStream_t s, const char* overlap_msg) {
+  const uint32_t N = ctx->p.N;
+  const uint64_t ctw = 2ull * towers * N;
+  if (!K) {
+    ctx->eval_chunk_count = 0;
+    return;
+  }
+  // the gather reads whole rows of the input while other workgroups write the output
+  if (words_overlap(ct_dev, ctw * K, out_dev, ctw * K)) throw Error{SHELFI_ERR_ARG, overlap_msg};
+  const KsArgs& a = l.args;
+  const auto bytes_of = [&](uint64_t kc) { return ks_scratch(a, N, kc); };
+  const uint64_t chains =
+      for_chunks(ctx, K, switches().eval_chunk_mib, bytes_of, [&](uint64_t k0, uint64_t kc, void* scratch) {
+        launch_rotate(a, ctx->dt, l.ext, l.dtf, rk.key, rk.key_sh, g, ct_dev + k0 * ctw, kc, out_dev + k0 * ctw,
+                      scratch, s);
+      });
+  SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
+  ctx->eval_chunk_count = chains;
+}
 }  // namespace
 
 }  // namespace shelfi
@@ -209,8 +234,9 @@ int shelfi_dev_encrypt(shelfi_ctx* ctx, const double* x_dev, size_t n, uint64_t*
     DeviceGuard g(ctx->device);
     const Params& p = ctx->p;
     hipStream_t s = (hipStream_t)stream;  // 0 = legacy default stream
-    const uint64_t K = (n + p.batch - 1) / p.batch;
+    const uint64_t K = (n + values_per_ct(p) - 1) / values_per_ct(p);
     if (!K) return;
+    require_pair_aligned(ctx, x_dev);
     uint32_t key[8];
     KeyWiper wipe(key);
     uint64_t g0;
@@ -221,7 +247,7 @@ int shelfi_dev_encrypt(shelfi_ctx* ctx, const double* x_dev, size_t n, uint64_t*
     const auto bytes_of = [&](uint64_t kc) { return encrypt_scratch_bytes(p, kc); };
     const auto run = [&](bool approx) {
       for_chunks(ctx, K, switches().dev_chunk_mib, bytes_of, [&](uint64_t k0, uint64_t kc, void* scratch) {
-        const uint64_t xs = k0 * p.batch, xn = std::min<uint64_t>(n - xs, kc * p.batch);
+        const uint64_t xs = k0 * values_per_ct(p), xn = std::min<uint64_t>(n - xs, kc * values_per_ct(p));
         uint64_t* ct = ct_dev + k0 * ct_words;
         if (approx)
           launch_encrypt_approx(p, ctx->dt, ctx->dk, x_dev + xs, xn, kc, ct, scratch, key, g0 + k0, s);
@@ -247,7 +273,8 @@ int shelfi_dev_encrypt_seeded(shelfi_ctx* ctx, const double* x_dev, size_t n, ui
     DeviceGuard g(ctx->device);
     const Params& p = ctx->p;
     hipStream_t s = (hipStream_t)stream;
-    const uint64_t K = (n + p.batch - 1) / p.batch;
+    const uint64_t K = (n + values_per_ct(p) - 1) / values_per_ct(p);
+    require_pair_aligned(ctx, x_dev);
     uint32_t key[8], seed[8];
     KeyWiper wipe(key);
     uint64_t g0;
@@ -259,7 +286,7 @@ int shelfi_dev_encrypt_seeded(shelfi_ctx* ctx, const double* x_dev, size_t n, ui
     const size_t c0_words = (size_t)p.L * p.N;
     const auto bytes_of = [&](uint64_t kc) { return seeded_encrypt_scratch_bytes(p, kc); };
     for_chunks(ctx, K, switches().dev_chunk_mib, bytes_of, [&](uint64_t k0, uint64_t kc, void* scratch) {
-      const uint64_t xs = k0 * p.batch, xn = std::min<uint64_t>(n - xs, kc * p.batch);
+      const uint64_t xs = k0 * values_per_ct(p), xn = std::min<uint64_t>(n - xs, kc * values_per_ct(p));
       launch_encrypt_seeded(p, ctx->dt, ctx->dk, x_dev + xs, xn, kc, c0_dev + k0 * c0_words, scratch, key, g0 + k0,
                             seed, k0, fl, s);
     });
@@ -300,15 +327,16 @@ int shelfi_dev_encode(shelfi_ctx* ctx, const double* x_dev, size_t n, uint32_t t
     const Params& p = ctx->p;
     require_towers(p, towers);
     if (!(scale > 0.0) || !std::isfinite(scale)) throw Error{SHELFI_ERR_ARG, "encode: the scale must be finite and positive"};
-    const uint64_t K = (n + p.batch - 1) / p.batch;
+    const uint64_t K = (n + values_per_ct(p) - 1) / values_per_ct(p);
     if (!K) return;
+    require_pair_aligned(ctx, x_dev);
     DeviceGuard g(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     const GenFlag fl = next_gen_flag(ctx);  // the call's own generation of the range words
     const size_t pt_words = (size_t)towers * p.N;
     const auto bytes_of = [&](uint64_t kc) { return encode_scratch_bytes(p, kc); };
     for_chunks(ctx, K, switches().dev_chunk_mib, bytes_of, [&](uint64_t k0, uint64_t kc, void* scratch) {
-      const uint64_t xs = k0 * p.batch, xn = std::min<uint64_t>(n - xs, kc * p.batch);
+      const uint64_t xs = k0 * values_per_ct(p), xn = std::min<uint64_t>(n - xs, kc * values_per_ct(p));
       launch_encode_plain(p, ctx->dt, x_dev + xs, xn, kc, towers, scale, pt_dev + k0 * pt_words, scratch, fl, s);
     });
     SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call; the range words are final
@@ -625,6 +653,21 @@ int shelfi_dev_rescale(shelfi_ctx* ctx, const uint64_t* in_dev, size_t K, uint32
   });
 }
 
+int shelfi_dev_conjugate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, uint64_t* out_dev,
+                         void* stream) {
+  if (!ctx || (K && (!ct_dev || !out_dev))) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    DeviceGuard dg(ctx->device);
+    LevelState& l = level(ctx, towers);
+    const uint32_t g = conjugation_galois(ctx->p.N);
+    const EvalState::RotKey* rk = find_rot(ctx->ev, g);
+    if (!rk) throw Error{SHELFI_ERR_STATE, "no conjugation key: call conjugateKeyGen() first"};
+    dev_galois_chains(ctx, l, *rk, g, ct_dev, K, towers, out_dev, (hipStream_t)stream,
+                      "conjugation input and output must not overlap");
+  });
+}
+
 int shelfi_dev_rotate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, int32_t index,
                       uint64_t* out_dev, void* stream) {
   if (!ctx || (K && (!ct_dev || !out_dev))) return SHELFI_ERR_ARG;
@@ -648,22 +691,7 @@ int shelfi_dev_rotate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_
     }
     LevelState& l = level(ctx, towers);
     const EvalState::RotKey& rk = require_rot(ctx, index, g);
-    if (!K) {
-      ctx->eval_chunk_count = 0;
-      return;
-    }
-    // the gather reads whole rows of the input while other workgroups write the output
-    if (words_overlap(ct_dev, ctw * K, out_dev, ctw * K))
-      throw Error{SHELFI_ERR_ARG, "rotation input and output must not overlap"};
-    const KsArgs& a = l.args;
-    const auto bytes_of = [&](uint64_t kc) { return ks_scratch(a, N, kc); };
-    const uint64_t chains =
-        for_chunks(ctx, K, switches().eval_chunk_mib, bytes_of, [&](uint64_t k0, uint64_t kc, void* scratch) {
-          launch_rotate(a, ctx->dt, l.ext, l.dtf, rk.key, rk.key_sh, g, ct_dev + k0 * ctw, kc, out_dev + k0 * ctw,
-                        scratch, s);
-        });
-    SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
-    ctx->eval_chunk_count = chains;
+    dev_galois_chains(ctx, l, rk, g, ct_dev, K, towers, out_dev, s, "rotation input and output must not overlap");
   });
 }
 

@@ -29,10 +29,25 @@ namespace shelfi {
 // len)], then BitReverse and /S (both folded into enc_prep).  First LOGR stages
 // on register columns (reading the learner's real vector directly), the rest in
 // LDS blocks of 2^fft_block_log(logS) complex values.
-template <int LOGR>
-__global__ __launch_bounds__(256) void fft_inv_cols(const double* __restrict__ x, uint64_t n,
-                                                    double2* __restrict__ buf, uint32_t logS,
-                                                    const double2* __restrict__ tw) {
+// Slot gi of the call's slot vectors, from its n values.  Real packing: x[gi] + 0i.  Complex packing (CX,
+// DESIGN.md §2.19): x[2 gi] + i x[2 gi + 1], one aligned 16-byte word; values at or beyond n read as 0 (the
+// pair whose first value is x[n - 1] keeps it and reads 0 for its second).
+template <bool CX>
+__device__ __forceinline__ double2 enc_slot(const double* __restrict__ x, uint64_t n, uint64_t gi) {
+  if constexpr (CX) {
+    if (2 * gi + 1 < n) return reinterpret_cast<const double2*>(x)[gi];
+    return make_double2(2 * gi < n ? x[2 * gi] : 0.0, 0.0);
+  } else {
+    return make_double2(gi < n ? x[gi] : 0.0, 0.0);
+  }
+}
+
+// (the three kernels that read x are bodies shared by a real and a complex (_cx) entry point, so the real
+// forms keep their names and their code)
+template <int LOGR, bool CX>
+__device__ __forceinline__ void fft_inv_cols_body(const double* __restrict__ x, uint64_t n,
+                                                  double2* __restrict__ buf, uint32_t logS,
+                                                  const double2* __restrict__ tw) {
   constexpr int R = 1 << LOGR;
   const uint32_t S = 1u << logS;
   const uint32_t BLK = S >> LOGR;
@@ -43,7 +58,7 @@ __global__ __launch_bounds__(256) void fft_inv_cols(const double* __restrict__ x
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const uint64_t gi = k * S + col + (uint64_t)r * BLK;
-    v[r] = make_double2(gi < n ? x[gi] : 0.0, 0.0);
+    v[r] = enc_slot<CX>(x, n, gi);
   }
 #pragma unroll
   for (int s = 0; s < LOGR; ++s) {
@@ -65,11 +80,24 @@ __global__ __launch_bounds__(256) void fft_inv_cols(const double* __restrict__ x
 #pragma unroll
   for (int r = 0; r < R; ++r) buf[k * S + col + (uint64_t)r * BLK] = v[r];
 }
+template <int LOGR>
+__global__ __launch_bounds__(256) void fft_inv_cols(const double* __restrict__ x, uint64_t n,
+                                                    double2* __restrict__ buf, uint32_t logS,
+                                                    const double2* __restrict__ tw) {
+  fft_inv_cols_body<LOGR, false>(x, n, buf, logS, tw);
+}
+template <int LOGR>
+__global__ __launch_bounds__(256) void fft_inv_cols_cx(const double* __restrict__ x, uint64_t n,
+                                                       double2* __restrict__ buf, uint32_t logS,
+                                                       const double2* __restrict__ tw) {
+  fft_inv_cols_body<LOGR, true>(x, n, buf, logS, tw);
+}
 
-__global__ __launch_bounds__(256) void fft_inv_blocks(const double* __restrict__ x, uint64_t n,
-                                                      double2* __restrict__ buf, uint32_t logS,
-                                                      uint32_t blkLog, int from_x,
-                                                      const double2* __restrict__ tw) {
+template <bool CX>
+__device__ __forceinline__ void fft_inv_blocks_body(const double* __restrict__ x, uint64_t n,
+                                                    double2* __restrict__ buf, uint32_t logS,
+                                                    uint32_t blkLog, int from_x,
+                                                    const double2* __restrict__ tw) {
   extern __shared__ __attribute__((aligned(16))) double2 smc[];
   const uint32_t S = 1u << logS, blk = 1u << blkLog;
   const uint32_t sh = logS - blkLog;
@@ -79,7 +107,7 @@ __global__ __launch_bounds__(256) void fft_inv_blocks(const double* __restrict__
   for (uint32_t i = threadIdx.x; i < blk; i += 256) {
     if (from_x) {
       const uint64_t gi = off + i;
-      smc[i] = make_double2(gi < n ? x[gi] : 0.0, 0.0);
+      smc[i] = enc_slot<CX>(x, n, gi);
     } else {
       smc[i] = buf[off + i];
     }
@@ -98,6 +126,18 @@ __global__ __launch_bounds__(256) void fft_inv_blocks(const double* __restrict__
     __syncthreads();
   }
   for (uint32_t i = threadIdx.x; i < blk; i += 256) buf[off + i] = smc[i];
+}
+__global__ __launch_bounds__(256) void fft_inv_blocks(const double* __restrict__ x, uint64_t n,
+                                                      double2* __restrict__ buf, uint32_t logS,
+                                                      uint32_t blkLog, int from_x,
+                                                      const double2* __restrict__ tw) {
+  fft_inv_blocks_body<false>(x, n, buf, logS, blkLog, from_x, tw);
+}
+__global__ __launch_bounds__(256) void fft_inv_blocks_cx(const double* __restrict__ x, uint64_t n,
+                                                         double2* __restrict__ buf, uint32_t logS,
+                                                         uint32_t blkLog, int from_x,
+                                                         const double2* __restrict__ tw) {
+  fft_inv_blocks_body<true>(x, n, buf, logS, blkLog, from_x, tw);
 }
 
 // FFTSpecialInv's second pass (encode, after fft_inv_cols): DIF half-sizes 2^(BL-1) .. 1.
@@ -122,8 +162,9 @@ __global__ __launch_bounds__(1 << (BL - 3)) void fft_inv_blocks_ct(double2* __re
 }
 
 // FFTSpecialInv (encode) of one 2^14-slot vector per workgroup: x (n doubles, zero-padded) -> buf [K][S].
-__global__ __launch_bounds__(1024) void fft_inv_whole(const double* __restrict__ x, uint64_t n,
-                                                      double2* __restrict__ buf, const double2* __restrict__ tw) {
+template <bool CX>
+__device__ __forceinline__ void fft_inv_whole_body(const double* __restrict__ x, uint64_t n,
+                                                   double2* __restrict__ buf, const double2* __restrict__ tw) {
   constexpr uint32_t S = 1u << kFftWholeLogS, BLK = 1024;
   constexpr int R = 16;
   __shared__ double lds[16 * kFftWholeRow];
@@ -131,12 +172,17 @@ __global__ __launch_bounds__(1024) void fft_inv_whole(const double* __restrict__
   const uint32_t T = threadIdx.x, w = T >> 6, l = T & 63;
   double2 a[R];
   // columns: DIF stages len S .. S/8 on column T (fft_inv_cols<4>)
-  const double* __restrict__ xk = x + k * S;
-  const uint32_t rem = n > k * S ? (uint32_t)std::min<uint64_t>(n - k * S, S) : 0u;
+  // (CX: the vector's 2 S values; enc_slot on the vector's own slice keeps 32-bit offsets)
+  constexpr uint32_t VS = CX ? 2 * S : S;
+  const double* __restrict__ xk = x + k * VS;
+  const uint32_t rem = n > k * VS ? (uint32_t)std::min<uint64_t>(n - k * VS, VS) : 0u;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const uint32_t i = T + (uint32_t)r * BLK;
-    a[r] = make_double2(i < rem ? xk[i] : 0.0, 0.0);
+    if constexpr (CX)
+      a[r] = 2 * i + 1 < rem ? reinterpret_cast<const double2*>(xk)[i] : make_double2(2 * i < rem ? xk[2 * i] : 0.0, 0.0);
+    else
+      a[r] = make_double2(i < rem ? xk[i] : 0.0, 0.0);
   }
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
@@ -170,6 +216,14 @@ __global__ __launch_bounds__(1024) void fft_inv_whole(const double* __restrict__
 #pragma unroll
     for (int m = 0; m < 4; ++m) g[4 * (l + 64 * q) + m] = c[m];
   }
+}
+__global__ __launch_bounds__(1024) void fft_inv_whole(const double* __restrict__ x, uint64_t n,
+                                                      double2* __restrict__ buf, const double2* __restrict__ tw) {
+  fft_inv_whole_body<false>(x, n, buf, tw);
+}
+__global__ __launch_bounds__(1024) void fft_inv_whole_cx(const double* __restrict__ x, uint64_t n,
+                                                         double2* __restrict__ buf, const double2* __restrict__ tw) {
+  fft_inv_whole_body<true>(x, n, buf, tw);
 }
 
 #define FFT_DISPATCH(LOGRV, KERNEL, ...)                                                   \
@@ -953,19 +1007,26 @@ size_t encrypt_scratch_bytes(const Params& p, uint64_t K) {
          K * (uint64_t)p.N * (sizeof(int64_t) + sizeof(int16_t)) + K * (8 + 8 + 16ull * p.L) + 64;
 }
 
-// encode's FFTSpecialInv of K slot vectors (x: n doubles, zero-padded) into fbuf [K][S] (complex)
+// encode's FFTSpecialInv of K slot vectors (x: n doubles, zero-padded) into fbuf [K][S] (complex); p.pack
+// picks the kernels that read x: one value per slot, or an interleaved (re, im) pair (the _cx entry points)
 void launch_encode_fft(const Params& p, const DeviceTables& dt, const double* x, uint64_t n, uint64_t K,
                        double2* fbuf, hipStream_t s) {
   const uint32_t logS = __builtin_ctz(p.batch);
   const uint32_t blkLog = fft_block_log(logS);
   const int logR = (int)(logS - blkLog);
   const size_t lds = sizeof(double2) << blkLog;
+  const bool cx = p.pack != 0;
   if (logS == kFftWholeLogS && K >= kFftWholeMinK && switches().fft_whole) {  // a workgroup per vector
-    hipLaunchKernelGGL(fft_inv_whole, dim3((uint32_t)K), dim3(1024), 0, s, x, n, fbuf, dt.fft_inv);
+    hipLaunchKernelGGL(cx ? fft_inv_whole_cx : fft_inv_whole, dim3((uint32_t)K), dim3(1024), 0, s, x, n, fbuf,
+                       dt.fft_inv);
   } else if (logR > 0) {
     const uint64_t nb = K * ((p.batch >> logR) / 256);
-    FFT_DISPATCH(logR, fft_inv_cols, dim3((uint32_t)nb), dim3(256), 0, s, x, n, fbuf, logS,
-                 dt.fft_inv);
+    if (cx) {
+      FFT_DISPATCH(logR, fft_inv_cols_cx, dim3((uint32_t)nb), dim3(256), 0, s, x, n, fbuf, logS, dt.fft_inv);
+    } else {
+      FFT_DISPATCH(logR, fft_inv_cols, dim3((uint32_t)nb), dim3(256), 0, s, x, n, fbuf, logS,
+                   dt.fft_inv);
+    }
     const bool fct = switches().fft_ct;
     if (fct && blkLog == 10)
       hipLaunchKernelGGL((fft_inv_blocks_ct<10, 3, 3, 2, 2>), dim3((uint32_t)(K << logR)), dim3(128), 0, s, fbuf,
@@ -977,8 +1038,8 @@ void launch_encode_fft(const Params& p, const DeviceTables& dt, const double* x,
       hipLaunchKernelGGL(fft_inv_blocks, dim3((uint32_t)(K << logR)), dim3(256), lds, s, x, n, fbuf,
                          logS, blkLog, 0, dt.fft_inv);
   } else {
-    hipLaunchKernelGGL(fft_inv_blocks, dim3((uint32_t)K), dim3(256), lds, s, x, n, fbuf, logS,
-                       blkLog, 1, dt.fft_inv);
+    hipLaunchKernelGGL(cx ? fft_inv_blocks_cx : fft_inv_blocks, dim3((uint32_t)K), dim3(256), lds, s, x, n, fbuf,
+                       logS, blkLog, 1, dt.fft_inv);
   }
   SHELFI_HIP(hipGetLastError());
 }

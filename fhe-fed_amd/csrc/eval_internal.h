@@ -62,6 +62,8 @@ EvkGenConst evk_gen_const(const Params& p, const EvalState& ev);
 uint32_t galois_element(uint32_t N, int32_t index);
 // the same for a slot rotation of this context; |index| must be below the batch size
 uint32_t rotation_galois(const shelfi_ctx* ctx, int32_t index);
+// conjugation's: X -> X^(2N - 1) = X^-1 (below 2^18, the width of the key stream's g field)
+inline uint32_t conjugation_galois(uint32_t N) { return 2u * N - 1u; }
 EvalState::RotKey* find_rot(EvalState* ev, uint32_t g);
 const EvalState::RotKey& require_rot(shelfi_ctx* ctx, int32_t index, uint32_t g);
 

@@ -241,6 +241,40 @@ int shelfi_set_rotation_key(shelfi_ctx* ctx, int32_t index, const uint64_t* key)
   });
 }
 
+// ---- conjugation: the key of g = 2N - 1, a rotation key listed under index 0 ----
+int shelfi_conjugate_keygen(shelfi_ctx* ctx) {
+  if (!ctx) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    require_keys(ctx);
+    DeviceGuard dg(ctx->device);
+    EvalState& ev = eval_state(ctx);
+    const uint32_t g = conjugation_galois(ctx->p.N);
+    if (!find_rot(&ev, g) && ev.rot.size() >= kMaxRotKeys)
+      throw Error{SHELFI_ERR_ARG, "a context holds at most 64 rotation keys"};
+    install_rot(ctx, ev, 0, g, switch_keygen(ctx, g).data());
+  });
+}
+
+int shelfi_get_conjugation_key(const shelfi_ctx* ctx, uint64_t* key) {
+  if (!ctx || !key) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    const EvalState::RotKey* r = find_rot(ctx->ev, conjugation_galois(ctx->p.N));
+    if (!r) throw Error{SHELFI_ERR_STATE, "no conjugation key: call conjugateKeyGen() first"};
+    std::memcpy(key, r->host.data(), r->host.size() * 8);
+  });
+}
+
+int shelfi_set_conjugation_key(shelfi_ctx* ctx, const uint64_t* key) {
+  if (!ctx || !key) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    DeviceGuard g(ctx->device);
+    install_rot(ctx, eval_state(ctx), 0, conjugation_galois(ctx->p.N), key);
+  });
+}
+
 int shelfi_get_eval_key(const shelfi_ctx* ctx, uint64_t* evk) {
   if (!ctx || !evk) return SHELFI_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);  // against a concurrent keygen / load replacing it

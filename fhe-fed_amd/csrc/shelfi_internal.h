@@ -99,7 +99,10 @@ struct Params {
   uint64_t psi[kMaxTowers] = {0};
   double delta = 0.0;  // (double)q[L-1]
   double sigma = 3.19;
+  uint32_t pack = 0;  // shelfi_set_slot_packing: SHELFI_PACK_REAL, or SHELFI_PACK_COMPLEX (two values per slot)
 };
+// values a ciphertext carries (V): one per slot, or both halves of every slot under complex packing
+inline uint64_t values_per_ct(const Params& p) { return (uint64_t)p.batch << (p.pack ? 1 : 0); }
 
 uint64_t powmod(uint64_t a, uint64_t e, uint64_t q);
 uint64_t invmod(uint64_t a, uint64_t q);
@@ -420,7 +423,9 @@ void launch_encrypt_approx(const Params& p, const DeviceTables& dt, const Device
                            uint64_t n, uint64_t K, uint64_t* ct, void* scratch, const uint32_t key[8],
                            uint64_t g0, hipStream_t s);
 size_t encrypt_scratch_bytes(const Params& p, uint64_t K);
-// encode's FFTSpecialInv of K slot vectors (x: n doubles, zero-padded) into fbuf [K][S] (encrypt.hip)
+// encode's FFTSpecialInv of K slot vectors (x: n doubles, zero-padded) into fbuf [K][S] (encrypt.hip); p.pack:
+// slot s of vector k holds x[k S + s] (real), or x[2 (k S + s)] + i x[2 (k S + s) + 1] read as one 16-byte word
+// (complex: x 16-byte aligned, K vectors cover 2 K S values)
 void launch_encode_fft(const Params& p, const DeviceTables& dt, const double* x, uint64_t n, uint64_t K,
                        double2* fbuf, hipStream_t s);
 // ---- plaintext operands (plain.hip) ----

@@ -51,6 +51,8 @@ typedef struct shelfi_info {
   uint64_t key_id;         /* 0 until keys are loaded/generated */
   int32_t keys_loaded;
   int32_t palisade_keys;   /* 1 if the keys came from PALISADE-format files */
+  uint32_t slot_packing;   /* SHELFI_PACK_REAL or SHELFI_PACK_COMPLEX (shelfi_set_slot_packing) */
+  uint32_t values_per_ct;  /* V: doubles one ciphertext carries, batch or 2 * batch */
 } shelfi_info;
 
 /* ---- library ------------------------------------------------------------ */
@@ -204,6 +206,24 @@ typedef struct {
 int shelfi_set_wire_format(shelfi_ctx* ctx, int format);
 /* The format encrypt answers in right now (0 .. 3; -1 for a NULL context). */
 int shelfi_get_wire_format(const shelfi_ctx* ctx);
+/* Slot packing, context state like the wire format.  SHELFI_PACK_REAL (the default): one
+ * double per slot, the slot's imaginary half unused, as the reference encodes.  SHELFI_PACK_COMPLEX: slot s of
+ * ciphertext k holds x[k V + 2 s] + i x[k V + 2 s + 1], V = 2 * batch values a ciphertext (shelfi_info's
+ * values_per_ct), so every call that takes or returns n doubles uses ceil(n / V) ciphertexts: shelfi_encrypt(_into),
+ * shelfi_decrypt, shelfi_fuse_decrypt, shelfi_dev_encrypt(_seeded), shelfi_dev_encode, shelfi_dev_decrypt(_level,
+ * _sum) and shelfi_dev_fuse_decrypt.  Values at or beyond n encode as 0; decrypt returns the first n.  The device
+ * calls then need x_dev / out_dev 16-byte aligned.  Everything between the two ends (the weighted average, the
+ * arena, the wire formats, partial decryption) is linear with real weights and runs unchanged; slot products are
+ * complex products (a norm is dot(u, conjugate(u)), shelfi_dev_conjugate).  Decode noise flooding estimates its
+ * sigma from the imaginary parts and cannot run on complex slots: with it enabled (the default) a complex-mode
+ * decrypt or fusion fails with SHELFI_ERR_STATE before anything runs -- turn it off with
+ * shelfi_set_decode_noise(ctx, 0, 1.0).  The mode is not recorded in a ciphertext: both ends must agree on it.
+ * An unknown mode: SHELFI_ERR_ARG. */
+#define SHELFI_PACK_REAL 0
+#define SHELFI_PACK_COMPLEX 1
+int shelfi_set_slot_packing(shelfi_ctx* ctx, int mode);
+/* The mode in force (-1 for a NULL context). */
+int shelfi_get_slot_packing(const shelfi_ctx* ctx);
 /* Host-only: parse an archive; residues [K][2][L][N] copied out when non-NULL. */
 int shelfi_palisade_parse(const uint8_t* archive, size_t len, shelfi_palisade_info* info,
                           uint64_t* residues);
@@ -540,9 +560,21 @@ int shelfi_dev_rotate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_
  * sum_{j < n} x[(i + j) mod batch].  n = 1 is a copy.  ct_dev and out_dev must not overlap. */
 int shelfi_dev_eval_sum(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, uint32_t n,
                         uint64_t* out_dev, void* stream);
+/* ---- conjugation: the automorphism X -> X^(2N - 1), which conjugates every slot ---- *
+ * Its key is a rotation key in all but its Galois element: made in the rotation keys' stream domain (nonce
+ * field g = 2N - 1), held among the context's 64 keys (shelfi_rotation_key_indices lists it as index 0) and
+ * dropped with them. */
+int shelfi_conjugate_keygen(shelfi_ctx* ctx);
+/* Export / import, as shelfi_get_rotation_key / shelfi_set_rotation_key (a keyless server is handed it this way). */
+int shelfi_get_conjugation_key(const shelfi_ctx* ctx, uint64_t* key);
+int shelfi_set_conjugation_key(shelfi_ctx* ctx, const uint64_t* key);
+/* out = (sigma_g(c0) + u0, u1), (u0, u1) = KeySwitch(sigma_g(c1)), g = 2N - 1: ct_dev, out_dev [K][2][towers][N] in
+ * HBM, not overlapping; chunked like shelfi_dev_rotate.  No key: SHELFI_ERR_STATE, "no conjugation key". */
+int shelfi_dev_conjugate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, uint64_t* out_dev,
+                         void* stream);
 /* The number of launch chains (chunks of the batch, each within the SHELFI_EVAL_CHUNK_MIB scratch budget,
  * 2048 by default) the last successful shelfi_dev_mult, shelfi_dev_gram, shelfi_dev_wsum_ct, shelfi_dev_rescale,
- * shelfi_dev_rotate or shelfi_dev_eval_sum on this context took.  0 after a call that enqueued no chain (K = 0, index 0,
+ * shelfi_dev_rotate, shelfi_dev_conjugate or shelfi_dev_eval_sum on this context took.  0 after a call that enqueued no chain (K = 0, index 0,
  * n = 1); a refused call leaves it unchanged.  For tests of the chunking. */
 uint64_t shelfi_eval_chunk_count(const shelfi_ctx* ctx);
 /* cc->EvalAdd(ct_a, ct_b) (mkhe.cpp:168, :368): out = a + b mod q_t over [K][2][towers][N]; out may be a
