@@ -510,7 +510,7 @@ class CKKS(Scheme):
         return self._mk_add(keys, True, "multiAddEvalMultKeys")
 
     def eval_chunk_count(self) -> int:
-        """Launch chains the last successful device.mult / gram / wsum_ct / rescale / rotate / eval_sum of this context
+        """Launch chains the last successful device.mult / gram / wsum_ct / poly_combine / rescale / rotate / eval_sum of this context
         took (shelfi_eval_chunk_count): 1 unless the batch's scratch exceeds SHELFI_EVAL_CHUNK_MIB
         (2048 by default); 0 after a call that enqueued none (K = 0, rotate by 0, eval_sum with n = 1)."""
         return int(self._lib.shelfi_eval_chunk_count(self._ctx))

@@ -58,6 +58,16 @@ class EvalKeyInfo(C.Structure):
                 ("keytag", C.c_char * 257)]
 
 
+class PolySchedule(C.Structure):
+    """shelfi_poly_schedule (include/shelfi.h): EvalPoly's plan."""
+    _fields_ = [("degree", C.c_uint32), ("giants", C.c_uint32), ("babies", C.c_uint32), ("rescales", C.c_uint32),
+                ("num_powers", C.c_uint32), ("power_n", C.c_uint32 * 10), ("power_a", C.c_uint32 * 10),
+                ("power_b", C.c_uint32 * 10), ("power_towers", C.c_uint32 * 10), ("power_scale", C.c_double * 10),
+                ("combine_towers", C.c_uint32), ("result_towers", C.c_uint32), ("combine_scale", C.c_double),
+                ("result_scale", C.c_double), ("const_scale", (C.c_double * 4) * 8),
+                ("table", ((C.c_uint64 * 16) * 4) * 8)]
+
+
 class PalisadeInfo(C.Structure):
     _fields_ = [
         ("ring_dim", C.c_uint32),
@@ -188,6 +198,11 @@ SIGNATURES = {
     "shelfi_gram_slice_count": (C.c_uint64, [C.c_void_p]),
     "shelfi_dev_wsum_ct": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, C.c_uint32,
                                      C.POINTER(C.c_void_p), C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "shelfi_poly_plan": (C.c_int, [C.c_uint32, u64p, C.c_uint32, f64p, C.c_uint32, C.c_uint32, C.c_double, C.c_double,
+                                   C.POINTER(PolySchedule)]),
+    "shelfi_dev_poly_combine": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32,
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32, u64p, C.c_size_t,
+                                          C.c_uint32, C.c_void_p, C.c_void_p]),
     "shelfi_dev_project": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t,
                                      C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "shelfi_dotp_slice_count": (C.c_uint64, [C.c_void_p]),

@@ -619,6 +619,111 @@ def wsum_ct(ckks, batches, weights, out=None):
     return out
 
 
+def _poly_plan(ckks, coeffs, towers, scale, combine_scale=None):
+    from . import poly
+
+    inf = ckks.info()
+    return poly.plan(inf["moduli"], inf["scale_bits"], coeffs, towers, scale, combine_scale)
+
+
+def _poly_powers(ckks, x, pl):
+    """{n: (P_n, scale)} along the plan's schedule: a product is wsum_ct at C = 1 -- the operand stored higher as
+    the update, read in place over the lower one's towers -- and one rescale."""
+    have = {}
+    for p in pl["powers"]:
+        if p["n"] == 1:
+            have[1] = (x, p["scale"])
+            continue
+        a, b = have[p["a"]][0], have[p["b"]][0]
+        hi, lo = (a, b) if a.shape[2] >= b.shape[2] else (b, a)
+        have[p["n"]] = (rescale(ckks, wsum_ct(ckks, [hi], [lo])), p["scale"])
+    return have
+
+
+def poly_powers(ckks, x, scale: float, degree: int):
+    """The powers of x [K][2][l][N] (at `scale`) that eval_poly of a degree-`degree` polynomial needs (needs
+    ckks.evalMultKeyGen()): {n: (P_n, scale_n)} for n = 1, 2, 3 as far as the degree reaches and n = 4, 8, 12, ..
+    below it, along shelfi_poly_plan's schedule (P_2 = P_1 P_1, P_3 = P_2 P_1, P_4 = P_2 P_2, P_{4g} = P_{4h}
+    P_{4(g-h)}).  Every product is one key switch a ciphertext and one rescale; P_n sits ceil(log2 n) towers below
+    x and its scale is the exact one.  The plan is made for the whole evaluation: an input with too few towers for the
+    combine's 1 or 2 rescales is refused here too, though the powers alone would fit."""
+    _check_ct(x, ckks, any_level=True)
+    if x.shape[0] == 0:
+        raise ValueError("EvalPoly needs at least one ciphertext")
+    if not 1 <= int(degree) <= 31:
+        raise ValueError("EvalPoly takes degrees 1..31")
+    return _poly_powers(ckks, x, _poly_plan(ckks, [0.0] * (int(degree) + 1), int(x.shape[2]), scale))
+
+
+def poly_combine(ckks, babies, giants, table, towers: int, out=None):
+    """shelfi_dev_poly_combine: babies = [P_1, ..] (1..3 batches), giants = [P_4, P_8, ..] (0..7), each
+    [K][2][its towers][N] with its towers >= `towers`, read in place; table: the plan's uint64 residues
+    [len(giants) + 1][4][towers].  out [K][2][towers][N] = (d0, d1) + KeySwitch(d2) of the summed giant-step
+    products (include/shelfi.h), at the plan's combine scale; out must overlap no operand.  Without giants no
+    evaluation key is needed."""
+    import numpy as np
+
+    torch = _torch()
+    babies, giants = list(babies), list(giants)
+    if not 1 <= len(babies) <= 3 or len(giants) > 7:
+        raise ValueError("EvalPoly's combine takes 1..3 baby-step and 0..7 giant-step powers")
+    ops = babies + giants
+    x = ops[0]
+    for t in ops:
+        _check_ct(t, ckks, x.shape[0] if t is not x else None, any_level=True)
+        if t.device != x.device:
+            raise ValueError("EvalPoly operands must live on the same device")
+    K, _, _, N = x.shape
+    towers = int(towers)
+    if K == 0:
+        raise ValueError("EvalPoly needs at least one ciphertext")
+    if towers < 1 or any(t.shape[2] < towers for t in ops):
+        raise ValueError("EvalPoly: every power must sit at the combine level or above")
+    tab = np.ascontiguousarray(table, dtype=np.uint64)
+    if tab.shape != (len(giants) + 1, 4, towers):
+        raise ValueError("EvalPoly's constants are [giants + 1][4][towers] uint64 residues")
+    if out is None:
+        out = torch.empty((K, 2, towers, N), dtype=x.dtype, device=x.device)
+    _check_ct(out, ckks, K, any_level=True)
+    if tuple(out.shape) != (K, 2, towers, N) or out.device != x.device:
+        raise ValueError("out must be a contiguous [K][2][towers][N] 64-bit tensor on the operands' device")
+    bp = (C.c_void_p * 3)(*[t.data_ptr() for t in babies])
+    bt = (C.c_uint32 * 3)(*[int(t.shape[2]) for t in babies])
+    gp = (C.c_void_p * 7)(*[t.data_ptr() for t in giants])
+    gt = (C.c_uint32 * 7)(*[int(t.shape[2]) for t in giants])
+    check(_lib.load().shelfi_dev_poly_combine(ckks._ctx, bp, bt, len(babies), gp, gt, len(giants),
+                                              tab.ctypes.data_as(_lib.u64p), K, towers, C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(_stream_ptr(x))), "dev_poly_combine")
+    return out
+
+
+def eval_poly(ckks, x, coeffs, scale: float, combine_scale=None):
+    """cc->EvalPoly: p(x) = sum_i coeffs[i] x^i in every slot of the K ciphertexts x [K][2][l][N] at `scale`,
+    degree 1..31 (needs ckks.evalMultKeyGen() from degree 2 on).  Returns (ct, scale_out).
+
+    Paterson-Stockmeyer with four baby steps: the powers x, x^2, x^3, x^4, x^8, x^12, .. (poly_powers: one key switch
+    and one rescale each), then ONE combine pass that sums every giant-step product x^{4g} q_g(x) as one tensor and
+    relinearizes it once per ciphertext (poly_combine), then 1 (degree <= 3) or 2 rescales.  Key switches per
+    ciphertext: 2 at degree 3, 4 at 7, 6 at 15 -- against degree - 1 for a term-by-term composition.  The constants
+    are encoded at scales that absorb each power's exact scale (SHELFI_FHE.poly.plan), so the differing rescales of
+    the powers cost no precision; combine_scale overrides the scale the terms are summed at (default 2^{2p}, or
+    2^{3p} above degree 3, p the context's scaling bits).
+    Levels: the result sits ceil(log2(highest power)) + rescales towers below x -- 3 at degree 3, 4 at 7, 6 at 15,
+    7 from 20 on; too few towers and constants too large for the combine level are ValueErrors.  Fit coefficients
+    on a normalised input (SHELFI_FHE.poly.fit)."""
+    _check_ct(x, ckks, any_level=True)
+    if x.shape[0] == 0:
+        raise ValueError("EvalPoly needs at least one ciphertext")
+    pl = _poly_plan(ckks, coeffs, int(x.shape[2]), scale, combine_scale)
+    have = _poly_powers(ckks, x, pl)
+    babies = [have[j][0] for j in range(1, pl["babies"] + 1)]
+    giants = [have[4 * g][0] for g in range(1, pl["giants"])]
+    out = poly_combine(ckks, babies, giants, pl["table"], pl["combine_towers"])
+    for _ in range(pl["rescales"]):
+        out = rescale(ckks, out)
+    return out, pl["result_scale"]
+
+
 def gram_sq_distances(ckks, G, n: int, out=None):
     """Krum's input from gram()'s result G [P][2][l][N] over n batches: the n (n - 1) / 2 ciphertexts
     G_ii + G_jj - 2 G_ij of ||u_i - u_j||^2 for i < j, in gram_pairs(n)'s order without the diagonal.  Index

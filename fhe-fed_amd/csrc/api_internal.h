@@ -188,6 +188,13 @@ struct StageRun {
   }
 };
 
+// -------------------------------------------------------- dev_arena.cpp ----
+// The next slot of the context's ring of small device buffers (shelfi_ctx::wl_*), at least `bytes` large, free to
+// be rewritten (the event of its last readers has been waited for).  ctx lock held.  The caller fills
+// ctx->wl_dev[slot] by a copy ordered on its stream and records ctx->wl_done[slot] on that stream behind the
+// kernels that read it: the slot is handed out again only after that event.
+int weight_ring_slot(shelfi_ctx* ctx, size_t bytes);
+
 // ------------------------------------------------------- call_state.cpp ----
 // W = (int64)((double)(float)w * Delta + 0.5) mod q_t as two 30-bit limbs, wl[t][2] for the p.L towers
 void weight_limbs(float w, const Params& p, uint32_t* wl);

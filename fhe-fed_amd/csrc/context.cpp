@@ -665,6 +665,8 @@ void shelfi_ctx_destroy(shelfi_ctx* ctx) {
       if (ctx->wl_dev[i]) (void)hipFree(ctx->wl_dev[i]);
     }
     dfree_t(ctx->unit_wl);
+    if (ctx->poly_pin) (void)hipHostFree(ctx->poly_pin);
+    ctx->poly_pin = nullptr;
     dfree_t(ctx->scratch);
     dfree_t(ctx->io);
     if (ctx->gather_host) (void)hipHostFree(ctx->gather_host);

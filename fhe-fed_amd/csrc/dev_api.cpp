@@ -1,8 +1,8 @@
 // dev_api.cpp — the device API (shelfi_dev_*: device buffers in, device buffers out, the caller's
 // stream): aggregation of separate batches, encrypt / decrypt and their threshold forms, the plaintext
 // operands, and the evaluation calls (EvalMult, EvalInnerProduct, the Gram matrix, ModReduce, Rotate, EvalSum,
-// EvalInnerProduct(ct, pt), EvalLinearWSum with encrypted weights, EvalAdd / Sub / Negate; DESIGN.md §2.11,
-// §2.13 - §2.16, §2.18).  The packed resident arena is dev_arena.cpp.
+// EvalInnerProduct(ct, pt), EvalLinearWSum with encrypted weights, EvalPoly's combine, EvalAdd / Sub / Negate;
+// DESIGN.md §2.11, §2.13 - §2.16, §2.18, §2.20).  The packed resident arena is dev_arena.cpp.
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -580,6 +580,95 @@ int shelfi_dev_wsum_ct(shelfi_ctx* ctx, const uint64_t* const* batches_dev, size
         for_chunks(ctx, K, switches().eval_chunk_mib, bytes_of, [&](uint64_t k0, uint64_t kc, void* scratch) {
           launch_wsum(a, ctx->dt, l.ext, l.dtf, ctx->ev->evk, ctx->ev->evk_sh, batches_dev, u_towers, weights_dev,
                       Kw == K && K > 1, (uint32_t)C, k0, kc, out_dev, scratch, s);
+        });
+    SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
+    ctx->eval_chunk_count = chains;
+  });
+}
+
+// EvalPoly's combine (poly.hip): the constants go to the device through the context's table ring
+// by a copy ordered on the stream; with giants the K outputs are cut into chains as shelfi_dev_wsum_ct's, a chain
+// the summed-tensor pass over its share of every power and one key switch; without, one launch left enqueued
+int shelfi_dev_poly_combine(shelfi_ctx* ctx, const uint64_t* const* babies_dev, const uint32_t* baby_towers,
+                            uint32_t nb, const uint64_t* const* giants_dev, const uint32_t* giant_towers, uint32_t ng,
+                            const uint64_t* table, size_t K, uint32_t towers, uint64_t* out_dev, void* stream) {
+  if (!ctx || !babies_dev || !baby_towers || !table || !out_dev || (ng && (!giants_dev || !giant_towers)))
+    return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    if (nb < 1 || nb > (uint32_t)kPolyMaxBabies) throw Error{SHELFI_ERR_ARG, "EvalPoly needs 1..3 baby-step powers"};
+    if (ng > (uint32_t)kPolyMaxGiants) throw Error{SHELFI_ERR_ARG, "EvalPoly takes 0..7 giant-step powers"};
+    for (uint32_t j = 0; j < nb; ++j)
+      if (!babies_dev[j]) throw Error{SHELFI_ERR_ARG, "EvalPoly: null operand"};
+    for (uint32_t g = 0; g < ng; ++g)
+      if (!giants_dev[g]) throw Error{SHELFI_ERR_ARG, "EvalPoly: null operand"};
+    DeviceGuard dg(ctx->device);
+    const Params& p = ctx->p;
+    if (ng) {
+      // a chain that cannot key-switch says so, before the key it can never hold is missed
+      if (!eval_state(ctx).ks_error.empty()) throw Error{SHELFI_ERR_ARG, eval_state(ctx).ks_error};
+      if (!ctx->ev || !ctx->ev->evk)
+        throw Error{SHELFI_ERR_STATE, "no evaluation key: call evalMultKeyGen() first"};
+    }
+    require_towers(p, towers);
+    const auto stored = [&](uint32_t t) {
+      if (t < towers || t > p.L)
+        throw Error{SHELFI_ERR_ARG, "EvalPoly: towers <= an operand's towers <= L (every power sits at the combine level or above)"};
+    };
+    for (uint32_t j = 0; j < nb; ++j) stored(baby_towers[j]);
+    for (uint32_t g = 0; g < ng; ++g) stored(giant_towers[g]);
+    if (!K) throw Error{SHELFI_ERR_ARG, "EvalPoly needs at least one ciphertext"};
+    // every operand is read by every chain's first pass: the output lies apart from all of them, over the towers
+    // each is stored with, not only the ones read
+    const uint32_t N = p.N;
+    const uint64_t ctw = 2ull * towers * N;
+    for (uint32_t j = 0; j < nb; ++j)
+      if (words_overlap(babies_dev[j], 2ull * baby_towers[j] * N * K, out_dev, ctw * K))
+        throw Error{SHELFI_ERR_ARG, "EvalPoly output must not overlap the operands"};
+    for (uint32_t g = 0; g < ng; ++g)
+      if (words_overlap(giants_dev[g], 2ull * giant_towers[g] * N * K, out_dev, ctw * K))
+        throw Error{SHELFI_ERR_ARG, "EvalPoly output must not overlap the operands"};
+    for (uint32_t g = 0; g <= ng; ++g)
+      for (uint32_t j = 0; j <= nb; ++j)
+        for (uint32_t t = 0; t < towers; ++t)
+          if (table[((size_t)g * 4 + j) * towers + t] >= p.q[t])
+            throw Error{SHELFI_ERR_ARG, "EvalPoly: a constant at or above its modulus"};
+    LevelState* l = ng ? &level(ctx, towers) : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    // the constants as a workgroup reads them, [towers][ng + 1][4], written into the ring slot's own pinned words
+    // (free once the slot is: the copy below is ordered before the kernels its event follows) and copied from
+    // there, so the copy is a DMA the host does not wait for
+    if (!ctx->poly_pin)
+      SHELFI_HIP(hipHostMalloc((void**)&ctx->poly_pin, (size_t)shelfi_ctx::kWeightRing * kPolyTableWords * 8,
+                               hipHostMallocDefault));
+    const size_t wt_words = (size_t)towers * (ng + 1) * 4;
+    const int slot = weight_ring_slot(ctx, wt_words * 8);
+    uint64_t* wt = ctx->poly_pin + (size_t)slot * kPolyTableWords;
+    for (uint32_t g = 0; g <= ng; ++g)
+      for (uint32_t j = 0; j < 4; ++j)
+        for (uint32_t t = 0; t < towers; ++t)
+          wt[((size_t)t * (ng + 1) + g) * 4 + j] = j <= nb ? table[((size_t)g * 4 + j) * towers + t] : 0;
+    SHELFI_HIP(hipMemcpyAsync(ctx->wl_dev[slot], wt, wt_words * 8, hipMemcpyHostToDevice, s));
+    // the slot's event goes behind whatever was enqueued, also when a launch below throws: the ring waits for it
+    // before it rewrites the slot
+    struct SlotDone {
+      hipEvent_t e;
+      hipStream_t s;
+      ~SlotDone() { (void)hipEventRecord(e, s); }
+    } slot_done{ctx->wl_done[slot], s};
+    const uint64_t* wt_dev = reinterpret_cast<const uint64_t*>(ctx->wl_dev[slot]);
+    if (!ng) {
+      launch_poly_combine(nullptr, ctx->dt, nullptr, nullptr, nullptr, nullptr, babies_dev, baby_towers, nb, nullptr,
+                          nullptr, 0, wt_dev, towers, p.logN, 0, K, out_dev, nullptr, s);
+      ctx->eval_chunk_count = 1;
+      return;
+    }
+    const KsArgs& a = l->args;
+    const auto bytes_of = [&](uint64_t kc) { return ks_scratch(a, N, kc); };
+    const uint64_t chains =
+        for_chunks(ctx, K, switches().eval_chunk_mib, bytes_of, [&](uint64_t k0, uint64_t kc, void* scratch) {
+          launch_poly_combine(&a, ctx->dt, &l->ext, l->dtf, ctx->ev->evk, ctx->ev->evk_sh, babies_dev, baby_towers, nb,
+                              giants_dev, giant_towers, ng, wt_dev, towers, p.logN, k0, kc, out_dev, scratch, s);
         });
     SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
     ctx->eval_chunk_count = chains;

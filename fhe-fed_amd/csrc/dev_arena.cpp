@@ -20,11 +20,21 @@ static int arena_weight_slot(shelfi_ctx* ctx, const float* w, size_t C, hipStrea
   for (size_t c = 0; c < C; ++c) weight_limbs(w[c], p, &wl[c * p.L * 2]);
   const int last = ctx->wl_last_slot;
   if (last >= 0 && ctx->wl_host[last] == wl) return last;
+  const size_t bytes = wl.size() * sizeof(uint32_t);
+  const int i = weight_ring_slot(ctx, bytes);
+  ctx->wl_host[i] = std::move(wl);  // stays alive until the slot is reused
+  SHELFI_HIP(hipMemcpyAsync(ctx->wl_dev[i], ctx->wl_host[i].data(), bytes, hipMemcpyHostToDevice, s));
+  return ctx->wl_last_slot = i;
+}
+
+// The ring itself, for any small table a kernel reads (the weight limbs above, EvalPoly's constants): the next
+// slot, waited for if the kernels that read it last are still running, grown to `bytes` if need be.  The caller
+// fills wl_dev[slot] by a copy ordered on its stream and records wl_done[slot] behind the kernels that read it.
+int weight_ring_slot(shelfi_ctx* ctx, size_t bytes) {
   const int i = ctx->wl_next;
   ctx->wl_next = (i + 1) % shelfi_ctx::kWeightRing;
   if (ctx->wl_done[i]) SHELFI_HIP(hipEventSynchronize(ctx->wl_done[i]));
   else SHELFI_HIP(hipEventCreateWithFlags(&ctx->wl_done[i], hipEventDisableTiming));
-  const size_t bytes = wl.size() * sizeof(uint32_t);
   if (ctx->wl_cap[i] < bytes) {
     if (ctx->wl_dev[i]) (void)hipFree(ctx->wl_dev[i]);
     ctx->wl_dev[i] = nullptr;
@@ -32,9 +42,7 @@ static int arena_weight_slot(shelfi_ctx* ctx, const float* w, size_t C, hipStrea
     SHELFI_HIP(hipMalloc(&ctx->wl_dev[i], bytes));
     ctx->wl_cap[i] = bytes;
   }
-  ctx->wl_host[i] = std::move(wl);  // stays alive until the slot is reused
-  SHELFI_HIP(hipMemcpyAsync(ctx->wl_dev[i], ctx->wl_host[i].data(), bytes, hipMemcpyHostToDevice, s));
-  ctx->wl_last_slot = i;
+  if (ctx->wl_last_slot == i) ctx->wl_last_slot = -1;  // (the slot's weights are about to be replaced)
   return i;
 }
 

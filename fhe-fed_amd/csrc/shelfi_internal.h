@@ -297,6 +297,7 @@ struct shelfi_ctx {
   hipEvent_t wl_done[kWeightRing] = {};
   std::vector<uint32_t> wl_host[kWeightRing];
   int wl_next = 0, wl_last_slot = -1;
+  uint64_t* poly_pin = nullptr;  // pinned host side of the ring for EvalPoly's constants: [kWeightRing][kPolyTableWords], created on first use
   uint32_t* unit_wl = nullptr;   // [16][kMaxTowers][2] limbs (1, 0): the packed exchange's unit-weight sum
   // scratch arena (grown on demand, never shrunk)
   void* scratch = nullptr;
@@ -602,6 +603,19 @@ void launch_wsum(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& d
                  const uint64_t* evk, const uint64_t* evk_sh, const uint64_t* const* u, uint32_t Lu,
                  const uint64_t* const* w, bool per_k, uint32_t C, uint64_t k0, uint64_t kc, uint64_t* out,
                  void* scratch, hipStream_t s);
+// EvalPoly's combine (poly.hip): ciphertexts [k0, k0 + kc) of out [K][2][Ll][N] from the powers babies[j - 1] = P_j
+// (nb <= kPolyMaxBabies) and giants[g - 1] = P_{4g} (ng <= kPolyMaxGiants), each [K][2][its towers][N] with its
+// towers >= Ll and its first Ll towers read in place; wt_dev [Ll][ng + 1][4] the plan's constants on the device;
+// out overlapping none.  ng = 0: one launch, no key, no scratch (a, dte, dtf, evk, scratch unused).  Otherwise one
+// launch chain: the summed-tensor pass and ONE key switch of the chain's kc ciphertexts, scratch =
+// ks_scratch_bytes(.., kc).
+constexpr int kPolyMaxBabies = 3, kPolyMaxGiants = 7;
+constexpr int kPolyTableWords = kMaxTowers * (kPolyMaxGiants + 1) * 4;  // the constants of one call, at most 4 KiB
+void launch_poly_combine(const KsArgs* a, const DeviceTables& dtq, const DeviceTables* dte, const DeviceTables* dtf,
+                         const uint64_t* evk, const uint64_t* evk_sh, const uint64_t* const* babies,
+                         const uint32_t* baby_towers, uint32_t nb, const uint64_t* const* giants,
+                         const uint32_t* giant_towers, uint32_t ng, const uint64_t* wt_dev, uint32_t Ll, uint32_t logN,
+                         uint64_t k0, uint64_t kc, uint64_t* out, void* scratch, hipStream_t s);
 // Rotation (rotate.hip): out = (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)) under the rotation key of
 // the Galois element g; ct, out [K][2][Ll][N], not overlapping; scratch = ks_scratch_bytes(.., K).
 void launch_rotate(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,

@@ -487,6 +487,64 @@ uint64_t shelfi_gram_slice_count(const shelfi_ctx* ctx);
 int shelfi_dev_wsum_ct(shelfi_ctx* ctx, const uint64_t* const* batches_dev, size_t C, size_t K, uint32_t u_towers,
                        const uint64_t* const* weights_dev, size_t Kw, uint32_t towers, uint64_t* out_dev,
                        void* stream);
+/* ---- cc->EvalPoly: Paterson-Stockmeyer with four baby steps and one key switch per output ----
+ * p(x) = sum_{g < G} x^{4g} q_g(x), deg q_g <= 3, G = ceil((d + 1) / 4) <= 8.  The powers P_1, P_2, P_3 (babies) and
+ * P_4, P_8, .. P_{4(G-1)} (giants) come from shelfi_dev_wsum_ct at C = 1 and shelfi_dev_rescale, in the order of
+ * the plan; shelfi_dev_poly_combine sums every giant-step product as one tensor and relinearizes it once. */
+#define SHELFI_POLY_MAX_DEGREE 31
+#define SHELFI_POLY_MAX_GIANTS 8
+#define SHELFI_POLY_MAX_POWERS 10 /* P_1, P_2, P_3 and seven giants */
+typedef struct shelfi_poly_schedule {
+  uint32_t degree, giants /* G */, babies /* min(d, 3) */, rescales /* r of the result: 1 when G = 1, else 2 */;
+  uint32_t num_powers;                            /* entries of power_*, every factor before its product */
+  uint32_t power_n[SHELFI_POLY_MAX_POWERS];       /* P_n = P_a P_b (n = 1: the input, a = b = 0) */
+  uint32_t power_a[SHELFI_POLY_MAX_POWERS], power_b[SHELFI_POLY_MAX_POWERS];
+  uint32_t power_towers[SHELFI_POLY_MAX_POWERS];  /* towers P_n is stored with */
+  double power_scale[SHELFI_POLY_MAX_POWERS];     /* its exact scale */
+  uint32_t combine_towers;                        /* t_c: the least towers over the powers */
+  uint32_t result_towers;                         /* t_c - r */
+  double combine_scale;                           /* S_c */
+  double result_scale;                            /* S_c / q_{t_c - 1} (/ q_{t_c - 2}) */
+  double const_scale[SHELFI_POLY_MAX_GIANTS][4];  /* c of term (g, j); 0 where 4 g + j > d */
+  uint64_t table[SHELFI_POLY_MAX_GIANTS][4][16];  /* W_{g,j} mod q_t, canonical, t < t_c; 0 elsewhere */
+} shelfi_poly_schedule;
+/* The plan (host only: no context, no device; the chain is given as for shelfi_special_primes).  moduli[0 ..
+ * num_towers) and scale_bits p are the context's (shelfi_ctx_info); coeffs[0 .. degree] the monomial coefficients
+ * a_0 .. a_d, 1 <= d <= 31; `towers` and `scale` the input ciphertext's l and s_1; combine_scale S_c, or 0 for the
+ * default 2^{2p} (G = 1) / 2^{3p} (G > 1).
+ * Schedule: P_2 = P_1 P_1, P_3 = P_2 P_1, P_4 = P_2 P_2, P_{4g} = P_{4h} P_{4(g-h)} with h the largest power of two
+ * below g.  A product is one mult at the lower operand's towers t and one rescale: towers t - 1, scale
+ * (s_a * s_b) / (double)q_{t-1} in IEEE double in that order; the depth of P_n is ceil(log2 n).
+ * Constants: term (g, j) carries a_{4g+j} at the double c = S_c, S_c / s_j, S_c / s_{4g}, (S_c / s_{4g}) / s_j, and
+ * W = sign(a) floor(|a| c + 1/2) for the EXACT product of the two doubles; table holds W mod q_t for t < t_c.  Every
+ * term of the combine then sits at S_c exactly, whatever the powers' rescales did to their scales.
+ * The result of shelfi_dev_poly_combine takes r rescales: towers t_c - r, scale S_c divided by q_{t_c-1} (then
+ * q_{t_c-2}) in double.  It costs ceil(log2(highest power)) + r levels: 3 at d = 3, 4 at d = 7, 6 at d = 15.
+ * d outside 1..31, a non-finite coefficient, a non-finite or non-positive scale, towers outside 1..num_towers, too
+ * few levels (a power below one tower, or t_c - r < 1) and any |W| >= Q_{t_c} / 2: SHELFI_ERR_ARG, *out untouched. */
+int shelfi_poly_plan(uint32_t num_towers, const uint64_t* moduli, uint32_t scale_bits, const double* coeffs,
+                     uint32_t degree, uint32_t towers, double scale, double combine_scale, shelfi_poly_schedule* out);
+/* The combine.  babies_dev[j - 1] = P_j, j = 1..nb (nb = 1..3); giants_dev[g - 1] = P_{4g}, g = 1..ng (ng = 0..7);
+ * each a batch [K][2][its towers][N] with its towers (baby_towers / giant_towers) >= `towers`, read in place at its
+ * own polynomial stride -- towers at and above `towers` are never touched.  table: HOST words [ng + 1][4][towers],
+ * canonical residues of W_{g,j} (entries with j > nb are not read).  Per ciphertext k, tower t < towers and
+ * evaluation point, mod q_t, with B_j = P_j and Gamma_g = P_{4g}:
+ *   q_{g,0} = W_{g,0} + sum_j W_{g,j} B_{j,0},  q_{g,1} = sum_j W_{g,j} B_{j,1}
+ *   d0 = q_{0,0} + sum_{g>=1} Gamma_{g,0} q_{g,0}
+ *   d1 = q_{0,1} + sum_{g>=1} (Gamma_{g,0} q_{g,1} + Gamma_{g,1} q_{g,0}),  d2 = sum_{g>=1} Gamma_{g,1} q_{g,1}
+ *   out[k] = (d0, d1) + KeySwitch(d2) under the installed evaluation key
+ * out_dev [K][2][towers][N]: ciphertexts of depth 2 at the plan's S_c for shelfi_dev_rescale.
+ * ng = 0: no tensor and no key switch -- the call needs no evaluation key, takes no scratch and returns with the work
+ * enqueued on `stream`.  Otherwise as shelfi_dev_wsum_ct: no evaluation key is SHELFI_ERR_STATE, the K outputs are
+ * cut into launch chains under SHELFI_EVAL_CHUNK_MIB (shelfi_eval_chunk_count reports them; no output bit depends
+ * on them), the context's scratch is used and `stream` synchronised before returning.
+ * nb outside 1..3, ng outside 0..7, towers outside 1..L, an operand stored with fewer than `towers` or more than L
+ * towers, K = 0, a NULL pointer (an array, a used entry, table, out_dev), out_dev overlapping any operand over its
+ * stored extent, a table entry >= its modulus, and (ng > 0) a chain with num_towers + special primes > 16:
+ * SHELFI_ERR_ARG; a refused call writes nothing. */
+int shelfi_dev_poly_combine(shelfi_ctx* ctx, const uint64_t* const* babies_dev, const uint32_t* baby_towers,
+                            uint32_t nb, const uint64_t* const* giants_dev, const uint32_t* giant_towers, uint32_t ng,
+                            const uint64_t* table, size_t K, uint32_t towers, uint64_t* out_dev, void* stream);
 /* cc->EvalInnerProduct(ct, pt) (EvalMult(ct, pt) + EvalAddMany) for every pair of C ciphertext batches and R
  * plaintext batches, as one call: out_dev [C R][2][towers][N], entry c R + r, holds per tower, coefficient and
  * component i the canonical sum_k u_{c,k,i} p_{r,k} mod q_t -- the projection of learner c's update on the known
