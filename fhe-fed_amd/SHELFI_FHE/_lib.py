@@ -226,6 +226,8 @@ SIGNATURES = {
     "shelfi_set_rotation_key": (C.c_int, [C.c_void_p, C.c_int32, u64p]),
     "shelfi_dev_rotate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int32, C.c_void_p,
                                     C.c_void_p]),
+    "shelfi_dev_rotate_many": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_int32),
+                                         C.c_size_t, C.c_void_p, C.c_void_p]),
     "shelfi_dev_eval_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
                                       C.c_void_p]),
     "shelfi_conjugate_keygen": (C.c_int, [C.c_void_p]),

@@ -785,6 +785,139 @@ def rotate(ckks, ct, r: int, out=None):
     return out
 
 
+ROTATE_MANY_MAX = 64  # shelfi_dev_rotate_many: the keys a context holds
+
+
+def rotate_many(ckks, ct, rs, out=None):
+    """The rotations of K ciphertexts by every index of rs from ONE digit decomposition of their c1 (hoisting:
+    PALISADE's EvalFastRotationPrecompute / EvalFastRotation): a tensor [R][K][2][l][N] whose entry r is an
+    ordinary batch holding rotate(ct, rs[r])'s slots -- within noise, not bit for bit: rotate decomposes
+    sigma_g(c1), this call c1 itself.  Needs the same keys (ckks.rotationKeyGen(rs)); indices
+    may repeat, 0 is a copy, 1 <= R <= 64.  out must not overlap ct.  Scale unchanged."""
+    torch = _torch()
+    _check_ct(ct, ckks, any_level=True)
+    rs = [int(r) for r in rs]
+    R = len(rs)
+    if not 1 <= R <= ROTATE_MANY_MAX:
+        raise ValueError("rotate_many takes 1..%d rotation indices" % ROTATE_MANY_MAX)
+    if any(not -(1 << 31) <= r < 1 << 31 for r in rs):
+        raise ValueError("rotation index must be below the batch size")
+    K, _, l, N = ct.shape
+    if out is None:
+        out = torch.empty((R, K, 2, l, N), dtype=ct.dtype, device=ct.device)
+    if (not out.is_cuda or not out.is_contiguous() or out.element_size() != 8 or tuple(out.shape) != (R, K, 2, l, N)
+            or out.device != ct.device):
+        raise ValueError("out must be a contiguous [R][K][2][l][N] 64-bit tensor on ct's device")
+    idx = (C.c_int32 * R)(*rs)
+    check(_lib.load().shelfi_dev_rotate_many(ckks._ctx, C.c_void_p(ct.data_ptr()), K, int(l), idx, R,
+                                             C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(ct))),
+          "dev_rotate_many")
+    return out
+
+
+def diagonals(M):
+    """The non-zero generalized diagonals of a batch x batch matrix, {d: M[s][(s + d) mod batch] over s}: the
+    form lin_transform takes, y = M x being y[s] = sum_d diag_d[s] x[(s + d) mod batch]."""
+    import numpy as np
+
+    M = np.asarray(M, dtype=np.float64)
+    if M.ndim != 2 or M.shape[0] != M.shape[1] or not M.shape[0]:
+        raise ValueError("diagonals() needs a square matrix")
+    n = M.shape[0]
+    s = np.arange(n)
+    out = {}
+    for d in range(n):
+        v = M[s, (s + d) % n]
+        if v.any():
+            out[d] = v.copy()
+    return out
+
+
+def _lin_plan(diags, babies=None):
+    """The baby-step / giant-step plan of a set of diagonals {d: vector of batch values}: (batch, b, {G: {i: d}})
+    with d = G + i (mod batch), 0 <= i < b and G a multiple of b.  The diagonal indices are taken modulo batch, as
+    0 .. batch - 1 or centred on 0, whichever spans less (a band around the main diagonal is centred)."""
+    import math
+
+    if not hasattr(diags, "items") or not len(diags):
+        raise ValueError("a linear transform needs a dict {diagonal index: vector of batch values}, not empty")
+    batch = len(next(iter(diags.values())))
+    if any(len(v) != batch for v in diags.values()):
+        raise ValueError("every diagonal must hold batch values")
+    up = sorted({int(d) % batch for d in diags})
+    if len(up) != len(diags):
+        raise ValueError("two diagonal indices are the same modulo batch")
+    centred = sorted(d - batch if d > batch // 2 else d for d in up)
+    reps = up if up[-1] - up[0] <= centred[-1] - centred[0] else centred
+    span = reps[-1] - reps[0] + 1
+    if babies is None:
+        b = 1 << max(0, round(math.log2(math.sqrt(span))))
+    else:
+        b = int(babies)
+        if b < 1 or b & (b - 1) or b > batch:
+            raise ValueError("babies must be a power of two in 1..batch")
+    plan = {}
+    for d in reps:
+        G = (d // b) * b
+        plan.setdefault(G, {})[d - G] = d % batch
+    return batch, b, plan
+
+
+def lin_transform_indices(diags, babies=None):
+    """The rotation indices lin_transform(ckks, ct, diags, babies=babies) needs keys for (rotationKeyGen's
+    argument): the baby steps it takes in one rotate_many and the giant steps it takes by rotate.  A plan that
+    needs more than the 64 keys a context holds is refused."""
+    _, b, plan = _lin_plan(diags, babies)
+    baby = sorted({i for steps in plan.values() for i in steps} - {0})
+    giant = sorted(set(plan) - {0})
+    keys = sorted(set(baby) | set(giant))
+    if len(keys) > ROTATE_MANY_MAX:
+        raise ValueError("this plan needs %d rotation keys, a context holds %d: babies b = %d with %d giant steps; "
+                         "choose another babies" % (len(keys), ROTATE_MANY_MAX, b, len(plan)))
+    return keys
+
+
+def lin_transform(ckks, ct, diags, scale=None, babies=None, out=None):
+    """A public batch x batch matrix applied to the slots of K ciphertexts [K][2][l][N], given by its diagonals
+    {d: vector} (diagonals(M)): y[s] = sum_d diags[d][s] x[(s + d) mod batch], by baby steps and giant steps.
+    One rotate_many makes the baby rotations x_i, i < b, from one decomposition; then per giant step G (a
+    multiple of b) one dot_plain sums x_i (.) encode(roll(diags[G + i], G)) over i, one rotate by G turns it, and
+    add collects the giants.  The plaintexts are encoded at `scale` (default q[l - 1]) and the sum is rescaled
+    once: the result [K][2][l - 1][N] is at the input's scale.  babies: b, a power of two (default: the one
+    nearest the square root of the diagonals' span).  Needs ckks.rotationKeyGen(lin_transform_indices(diags,
+    babies)) and l >= 2; real slot packing only."""
+    torch = _torch()
+    _check_ct(ct, ckks, any_level=True)
+    K, _, l, N = ct.shape
+    inf = ckks.info()
+    batch, b, plan = _lin_plan(diags, babies)
+    lin_transform_indices(diags, babies)  # the 64-key limit, by name
+    if batch != inf["batch"] or inf["values_per_ct"] != inf["batch"]:
+        raise ValueError("the diagonals must hold batch = %d values (real slot packing)" % inf["batch"])
+    if l < 2:
+        raise ValueError("a linear transform spends one level: the input needs at least 2 towers")
+    if K == 0:
+        raise ValueError("a linear transform needs at least one ciphertext")
+    scale = float(inf["moduli"][l - 1] if scale is None else scale)
+    dg = {int(d) % batch: torch.as_tensor(v, dtype=torch.float64).to(ct.device) for d, v in diags.items()}
+    baby = sorted({i for steps in plan.values() for i in steps})
+    rots = rotate_many(ckks, ct, baby)  # [len(baby)][K][2][l][N]
+    acc = None
+    for G in sorted(plan):
+        steps = sorted(plan[G])
+        pts = encode(ckks, torch.cat([torch.roll(dg[plan[G][i]], G) for i in steps]).contiguous(), towers=l,
+                     scale=scale)  # [len(steps)][l][N]
+        sel = [baby.index(i) for i in steps]
+        part = torch.empty_like(ct)
+        for k in range(K):  # the plaintext step per ciphertext: its stacked baby rotations against the diagonals
+            stack = rots[sel, k] if sel != list(range(len(baby))) else rots[:, k]
+            dot_plain(ckks, stack.contiguous(), pts, out=part[k:k + 1])
+        if G:
+            part = rotate(ckks, part, G)
+        acc = part if acc is None else add(ckks, acc, part, out=acc)
+    return rescale(ckks, acc, out=out)
+
+
 def conj(ckks, ct, out=None):
     """The complex conjugate of every slot of K ciphertexts of any level: the automorphism X -> X^(2N - 1) and
     its key switch, (sigma(c0) + u0, u1) with (u0, u1) = KeySwitch(sigma(c1)).  Needs ckks.conjugateKeyGen().

@@ -1,8 +1,8 @@
 // dev_api.cpp — the device API (shelfi_dev_*: device buffers in, device buffers out, the caller's
 // stream): aggregation of separate batches, encrypt / decrypt and their threshold forms, the plaintext
 // operands, and the evaluation calls (EvalMult, EvalInnerProduct, the Gram matrix, ModReduce, Rotate, EvalSum,
-// EvalInnerProduct(ct, pt), EvalLinearWSum with encrypted weights, EvalPoly's combine, EvalAdd / Sub / Negate;
-// DESIGN.md §2.11, §2.13 - §2.16, §2.18, §2.20).  The packed resident arena is dev_arena.cpp.
+// EvalInnerProduct(ct, pt), EvalLinearWSum with encrypted weights, EvalPoly's combine, hoisted rotations, EvalAdd /
+// Sub / Negate).  The packed resident arena is dev_arena.cpp.
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -425,7 +425,7 @@ int shelfi_dev_ntt(shelfi_ctx* ctx, uint64_t* polys_dev, size_t P, int inverse, 
   });
 }
 
-// ---- the evaluation calls (keyswitch.hip, rotate.hip): each cuts its K ciphertexts into
+// ---- the evaluation calls (keyswitch.hip, rotate.hip, hoist.hip): each cuts its K ciphertexts into
 // launch chains under SHELFI_EVAL_CHUNK_MIB and leaves their number in ctx->eval_chunk_count ----
 int shelfi_dev_mult(shelfi_ctx* ctx, const uint64_t* a_dev, const uint64_t* b_dev, size_t K, uint32_t towers,
                     uint64_t* out_dev, void* stream) {
@@ -781,6 +781,78 @@ int shelfi_dev_rotate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_
     LevelState& l = level(ctx, towers);
     const EvalState::RotKey& rk = require_rot(ctx, index, g);
     dev_galois_chains(ctx, l, rk, g, ct_dev, K, towers, out_dev, s, "rotation input and output must not overlap");
+  });
+}
+
+int shelfi_dev_rotate_many(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, const int32_t* indices,
+                           size_t R, uint64_t* out_dev, void* stream) {
+  if (!ctx || (R && !indices) || (K && R && (!ct_dev || !out_dev))) return SHELFI_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return guarded([&] {
+    DeviceGuard dg(ctx->device);
+    const uint32_t N = ctx->p.N;
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t ctw = 2ull * towers * N;
+    require_towers(ctx->p, towers);
+    if (R > kMaxRotKeys) throw Error{SHELFI_ERR_ARG, "rotate_many takes at most 64 rotations a call"};
+    struct Rot {
+      size_t r;  // its place in out
+      uint32_t g, ginv;
+      const EvalState::RotKey* rk;
+    };
+    std::vector<Rot> rots;  // every key is looked up before anything is enqueued
+    std::vector<size_t> copies;
+    bool have_level = false;
+    for (size_t r = 0; r < R; ++r) {
+      const uint32_t g = rotation_galois(ctx, indices[r]);
+      if (!indices[r]) {
+        copies.push_back(r);
+        continue;
+      }
+      // a chain that cannot key-switch says so, before the keys it can never hold are missed
+      if (!have_level) level(ctx, towers), have_level = true;
+      rots.push_back(Rot{r, g, galois_element(N, -indices[r]), &require_rot(ctx, indices[r], g)});
+    }
+    ctx->eval_chunk_count = 0;
+    if (!K || !R) return;
+    if (words_overlap(ct_dev, ctw * K, out_dev, ctw * K * R))
+      throw Error{SHELFI_ERR_ARG, "rotation input and output must not overlap"};
+    level_q(ctx, towers);
+    for (size_t r : copies)  // index 0: the input itself
+      SHELFI_HIP(hipMemcpyAsync(out_dev + r * K * ctw, ct_dev, ctw * K * 8, hipMemcpyDeviceToDevice, s));
+    uint64_t chains = 0;
+    if (!rots.empty()) {
+      LevelState& l = level(ctx, towers);
+      const KsArgs& a = l.args;
+      // rotations in flight behind one decomposition: as many accumulator sets as one ciphertext's share of the
+      // budget holds beside the decomposition (at least one), so a long list splits over rotation groups
+      // before a chain exceeds SHELFI_EVAL_CHUNK_MIB
+      // (the floor, as chunk_split's: one ciphertext with one rotation in flight runs even when that alone is over
+      // the budget -- include/shelfi.h says so)
+      const uint64_t budget = (uint64_t)switches().eval_chunk_mib << 20;
+      const uint64_t sh1 = hoist_shared_bytes(a, 1), acc1 = hoist_acc_bytes(a, 1);
+      const uint64_t fit = budget > sh1 ? (budget - sh1) / acc1 : 0;
+      const size_t Rg = (size_t)std::min<uint64_t>({rots.size(), (uint64_t)kHoistMaxGroup, std::max<uint64_t>(fit, 1)});
+      const auto bytes_of = [&](uint64_t kc) { return hoist_shared_bytes(a, kc) + Rg * hoist_acc_bytes(a, kc); };
+      const uint64_t kchains =
+          for_chunks(ctx, K, switches().eval_chunk_mib, bytes_of, [&](uint64_t k0, uint64_t kc, void* scratch) {
+            launch_hoist_decompose(a, ctx->dt, l.ext, l.dtf, ct_dev + k0 * ctw, kc, scratch, s);
+            for (size_t i0 = 0; i0 < rots.size(); i0 += Rg) {
+              HoistGroup grp{};
+              grp.n = (uint32_t)std::min(Rg, rots.size() - i0);
+              bool contiguous = kc == K;
+              for (uint32_t i = 0; i < grp.n; ++i) {
+                const Rot& rt = rots[i0 + i];
+                grp.r[i] = HoistRot{rt.rk->key, rt.rk->key_sh, out_dev + (rt.r * K + k0) * ctw, rt.g, rt.ginv};
+                contiguous = contiguous && rt.r == rots[i0].r + i;
+              }
+              launch_hoist_rotations(a, ctx->dt, l.ext, grp, contiguous, ct_dev + k0 * ctw, kc, scratch, s);
+            }
+          });
+      chains = kchains * ((rots.size() + Rg - 1) / Rg);
+    }
+    SHELFI_HIP(hipStreamSynchronize(s));  // scratch is reused by the next call
+    ctx->eval_chunk_count = chains;
   });
 }
 

@@ -596,6 +596,24 @@ __device__ __forceinline__ void ks_intt_block_out(uint64_t* sm, uint32_t blkLog,
   }
 }
 
+// ---- the key switch's digits (keyswitch.hip, hoist.hip) ----
+// Digit j of a level owns towers [j alpha, j alpha + cnt) of Q_l; its "foreign" towers (the
+// rest of Q_l, then P) are the ones ModUp must produce, stored in that order (index u =
+// t < s ? t : t - cnt) so every NTT over them is a plain batch with per-digit tables.
+__device__ __forceinline__ void digit_span(const KsArgs& a, uint32_t j, uint32_t& s, uint32_t& cnt) {
+  s = j * a.alpha;
+  cnt = min(a.alpha, a.Ll - s);
+}
+__device__ __forceinline__ uint64_t ext_base(const KsArgs& a, uint32_t j, uint64_t K) {
+  uint64_t base = 0;
+  for (uint32_t i = 0; i < j; ++i) {
+    uint32_t s, cnt;
+    digit_span(a, i, s, cnt);
+    base += (uint64_t)(a.T - cnt) * K;  // in polynomials
+  }
+  return base << a.logN;
+}
+
 // The automorphism sigma_g: X -> X^g (g odd) on a polynomial in EVALUATION, in the NTT's own
 // (bit-reversed) order: out[j] = in[galois_src(j)], where position j holds the value at
 // psi^(2 brev(j) + 1) and sigma_g(a)(psi^e) = a(psi^(g e)).  Aligned runs of 2^k positions map onto

@@ -49,22 +49,7 @@ __device__ __forceinline__ uint64_t red128(du128 acc, const TowerConst& c) {
 }
 __device__ __forceinline__ du128 mul128(uint64_t a, uint64_t b) { return (du128)a * b; }
 
-// Digit j of a level owns towers [j alpha, j alpha + cnt) of Q_l; its "foreign" towers (the
-// rest of Q_l, then P) are the ones ModUp must produce, stored in that order (index u =
-// t < s ? t : t - cnt) so every NTT over them is a plain batch with per-digit tables.
-__device__ __forceinline__ void digit_span(const KsArgs& a, uint32_t j, uint32_t& s, uint32_t& cnt) {
-  s = j * a.alpha;
-  cnt = min(a.alpha, a.Ll - s);
-}
-__device__ __forceinline__ uint64_t ext_base(const KsArgs& a, uint32_t j, uint64_t K) {
-  uint64_t base = 0;
-  for (uint32_t i = 0; i < j; ++i) {
-    uint32_t s, cnt;
-    digit_span(a, i, s, cnt);
-    base += (uint64_t)(a.T - cnt) * K;  // in polynomials
-  }
-  return base << a.logN;
-}
+// (digit_span / ext_base, the digits' towers and where their foreign towers sit in ext: dev_common.h)
 
 // ------------------------------------------------ tensor + first INTT pass ----
 // One workgroup per (ct, tower, block): c0 = a0 b0 and c1 = a0 b1 + a1 b0 go to `out`,
@@ -496,9 +481,7 @@ __global__ __launch_bounds__(256) void ks_finish_blocks_ct(const uint64_t* __res
 }
 
 size_t ks_scratch_bytes(uint32_t Ll, uint32_t kP, uint32_t dn, uint32_t alpha, uint32_t N, uint64_t K) {
-  const uint64_t T = Ll + kP;
-  uint64_t ext = 0;
-  for (uint32_t j = 0; j < dn; ++j) ext += T - std::min(alpha, Ll - j * alpha);
+  const uint64_t ext = ks_ext_towers(Ll, kP, dn, alpha);
   // d2e | d2c | ext | accQ | accP | z
   return K * (uint64_t)N * 8 * (2ull * Ll + ext + 2ull * Ll + 2ull * kP + 2ull * Ll) + 64;
 }
@@ -509,9 +492,7 @@ KsScratch ks_scratch_layout(const KsArgs& a, uint64_t K, void* scratch) {
   k.d2e = reinterpret_cast<uint64_t*>(scratch);
   k.d2c = k.d2e + KN * a.Ll;
   k.ext = k.d2c + KN * a.Ll;
-  uint64_t next = 0;
-  for (uint32_t j = 0; j < a.dn; ++j) next += a.T - std::min(a.alpha, a.Ll - j * a.alpha);
-  k.accQ = k.ext + KN * next;
+  k.accQ = k.ext + KN * ks_ext_towers(a.Ll, a.kP, a.dn, a.alpha);
   k.accP = k.accQ + KN * 2 * a.Ll;
   k.z = k.accP + KN * 2 * a.kP;
   return k;
@@ -532,6 +513,78 @@ void launch_eval_mult(const KsArgs& a, const DeviceTables& dtq, const DeviceTabl
   launch_key_switch(a, dtq, dte, dtf, evk, evk_sh, K, out, scratch, s);
 }
 
+static dim3 ks_grid(uint64_t rows, uint32_t per_row) {
+  const uint64_t b = rows * per_row;
+  if (b > 0x7FFFFFFFull) throw Error{SHELFI_ERR_ARG, "key switch batch too large"};
+  return dim3((uint32_t)b);
+}
+// ModUp fused with the first NTT stages when the ring has a columns pass and digits / special primes
+// have <= 2 towers (LOGR 5 would hold 2 x 32 converted rows + 32 lanes: 256 VGPRs, 1 wave/SIMD)
+static bool ks_fuse_cols(const KsArgs& a) {
+  const int logR = (int)(a.logN - ntt_block_log(a.logN));
+  return logR > 0 && logR <= 4 && a.alpha <= 2 && a.kP <= 2;
+}
+
+// The decomposition of launch_key_switch: d2c [K][Ll][N] (after the first INTT pass) through the INTT
+// columns, then ModUp of every digit's foreign towers with their first NTT stages into ext: fused
+// (ks_fuse_cols), else modup_kernel, then a columns pass per digit (none for a single-block ring,
+// whose blocks pass runs every stage).
+void launch_ks_modup(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,
+                     uint64_t K, uint64_t* d2c, uint64_t* ext, hipStream_t s) {
+  const uint32_t N = 1u << a.logN, bpr = N >> 8;
+  const int logR = (int)(a.logN - ntt_block_log(a.logN));
+  launch_ntt_cols(d2c, K * a.Ll, a.Ll, a.logN, true, dtq, s);
+  if (ks_fuse_cols(a)) {
+    const uint64_t rows = (uint64_t)a.dn * K, per = (N >> logR) / 256;
+    NTT_DISPATCH_KS(logR, modup_cols_kernel, ks_grid(rows, (uint32_t)per), dim3(256), 0, s, d2c, K, a, dte.psi_rev,
+                    dte.psi_rev_sh, ext);
+  } else {
+    hipLaunchKernelGGL(modup_kernel, ks_grid((uint64_t)a.dn * K, bpr), dim3(256), 0, s, d2c, K, a, ext);
+    uint64_t* e = ext;
+    for (uint32_t j = 0; j < a.dn && logR > 0; ++j) {
+      const uint32_t Tf = a.T - std::min(a.alpha, a.Ll - j * a.alpha);
+      launch_ntt_cols(e, K * Tf, Tf, a.logN, false, dtf[j], s);
+      e += (K * N) * Tf;
+    }
+  }
+  SHELFI_HIP(hipGetLastError());
+}
+
+// ModDown of launch_key_switch over K accumulators: INTT of the P part accP [K][2][kP][N], the P -> Q_l
+// conversion into z [K][2][Ll][N] with its first NTT stages.
+void launch_ks_moddown(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, uint64_t K, uint64_t* accP,
+                       uint64_t* z, hipStream_t s) {
+  const uint32_t N = 1u << a.logN, bpr = N >> 8;
+  const int logR = (int)(a.logN - ntt_block_log(a.logN));
+  launch_ntt(accP, K * 2 * a.kP, a.kP, a.logN, true, tower_view(dte, a.Ll, N), s);
+  if (ks_fuse_cols(a)) {
+    NTT_DISPATCH_KS(logR, moddown_cols_kernel, ks_grid(K * 2, (uint32_t)((N >> logR) / 256)), dim3(256), 0, s, accP,
+                    a, dtq.psi_rev, dtq.psi_rev_sh, z);
+  } else {
+    hipLaunchKernelGGL(moddown_kernel, ks_grid(K * 2, bpr), dim3(256), 0, s, accP, a, z);
+    SHELFI_HIP(hipGetLastError());
+    launch_ntt_cols(z, K * 2 * a.Ll, a.Ll, a.logN, false, dtq, s);
+  }
+  SHELFI_HIP(hipGetLastError());
+}
+
+// z's last NTT stages and the ModDown finish: out [K][2][Ll][N] += (accQ - NTT(z)) P^-1
+void launch_ks_finish(const KsArgs& a, const DeviceTables& dtq, uint64_t K, const uint64_t* z, const uint64_t* accQ,
+                      uint64_t* out, hipStream_t s) {
+  const uint32_t blkLog = ntt_block_log(a.logN), sh = a.logN - blkLog, nb = 1u << sh;
+  const size_t lds = sizeof(uint64_t) << blkLog;
+  if (sh > 0 && blkLog == 11 && dtq.red_ok)
+    hipLaunchKernelGGL((ks_finish_blocks_ct<11, 3, 3, 3, 2>), ks_grid(K * 2 * a.Ll, nb), dim3(256), 0, s, z, accQ, a,
+                       dtq.tw_fwd_blk, out);
+  else if (sh > 0 && blkLog == 12 && dtq.red_ok)
+    hipLaunchKernelGGL((ks_finish_blocks_ct<12, 3, 3, 3, 3>), ks_grid(K * 2 * a.Ll, nb), dim3(256), 0, s, z, accQ, a,
+                       dtq.tw_fwd_blk, out);
+  else
+    hipLaunchKernelGGL(ks_finish_blocks_kernel, ks_grid(K * 2 * a.Ll, nb), dim3(256), lds, s, z, accQ, a, blkLog,
+                       dtq.psi_rev, dtq.psi_rev_sh, out);
+  SHELFI_HIP(hipGetLastError());
+}
+
 // The HYBRID key switch behind a first pass (the tensor product's, or rotate.hip's automorphism) that
 // left the polynomial to switch in the scratch (d2e: EVALUATION, d2c: after the first INTT pass) and
 // the terms the result is added to in `out`: INTT columns, ModUp, the key inner product, ModDown,
@@ -540,74 +593,27 @@ void launch_key_switch(const KsArgs& a, const DeviceTables& dtq, const DeviceTab
                        const uint64_t* evk, const uint64_t* evk_sh, uint64_t K, uint64_t* out, void* scratch,
                        hipStream_t s) {
   if (!K) return;
-  const uint32_t N = 1u << a.logN, bpr = N >> 8;
-  const uint32_t blkLog = ntt_block_log(a.logN), sh = a.logN - blkLog;
+  const uint32_t blkLog = ntt_block_log(a.logN), sh = a.logN - blkLog, nb = 1u << sh;
   const size_t lds = sizeof(uint64_t) << blkLog;
-  const uint64_t KN = K * N;
   const KsScratch ks = ks_scratch_layout(a, K, scratch);
-  uint64_t *d2e = ks.d2e, *d2c = ks.d2c, *ext = ks.ext, *accQ = ks.accQ, *accP = ks.accP, *z = ks.z;
-  auto grid = [&](uint64_t rows, uint32_t per_row) {
-    const uint64_t b = rows * per_row;
-    if (b > 0x7FFFFFFFull) throw Error{SHELFI_ERR_ARG, "key switch batch too large"};
-    return dim3((uint32_t)b);
-  };
-  const uint32_t nb = 1u << sh;
-  launch_ntt_cols(d2c, K * a.Ll, a.Ll, a.logN, true, dtq, s);
-  // ModUp of every digit's foreign towers with their first NTT stages: fused when the ring has
-  // a columns pass and digits / special primes have <= 2 towers; else modup_kernel, then a
-  // columns pass per digit (none for a single-block ring, whose blocks pass runs every stage)
-  const int logR = (int)sh;
-  // (LOGR 5 would hold 2 x 32 converted rows + 32 lanes: 256 VGPRs, 1 wave/SIMD; unfused there)
-  const bool fuse_cols = logR > 0 && logR <= 4 && a.alpha <= 2 && a.kP <= 2;
-  if (fuse_cols) {
-    const uint64_t rows = (uint64_t)a.dn * K, per = (N >> logR) / 256;
-    NTT_DISPATCH_KS(logR, modup_cols_kernel, grid(rows, (uint32_t)per), dim3(256), 0, s, d2c, K, a, dte.psi_rev,
-                    dte.psi_rev_sh, ext);
-  } else {
-    hipLaunchKernelGGL(modup_kernel, grid((uint64_t)a.dn * K, bpr), dim3(256), 0, s, d2c, K, a, ext);
-    uint64_t* e = ext;
-    for (uint32_t j = 0; j < a.dn && logR > 0; ++j) {
-      const uint32_t Tf = a.T - std::min(a.alpha, a.Ll - j * a.alpha);
-      launch_ntt_cols(e, K * Tf, Tf, a.logN, false, dtf[j], s);
-      e += KN * Tf;
-    }
-  }
-  SHELFI_HIP(hipGetLastError());
+  launch_ks_modup(a, dtq, dte, dtf, K, ks.d2c, ks.ext, s);
   // last NTT stages + the key inner product (one LDS block per digit; > 64 KiB only for
   // 2^12-element blocks with 3 digits, which a gfx950 workgroup may still declare)
   if (sh > 0 && blkLog == 11 && dte.red_ok) {
-    hipLaunchKernelGGL((ks_inner_blocks_ct<11, 3, 3, 3, 2>), grid(K * a.T, nb), dim3(256),
-                       sizeof(uint64_t) * lpad_size(11) * a.dn, s, d2e, ext, K, a, dte.tw_fwd_blk, evk, evk_sh, accQ,
-                       accP);
+    hipLaunchKernelGGL((ks_inner_blocks_ct<11, 3, 3, 3, 2>), ks_grid(K * a.T, nb), dim3(256),
+                       sizeof(uint64_t) * lpad_size(11) * a.dn, s, ks.d2e, ks.ext, K, a, dte.tw_fwd_blk, evk, evk_sh,
+                       ks.accQ, ks.accP);
   } else {
     if (lds * a.dn > 65536)
       SHELFI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ks_inner_blocks_kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds * a.dn)));
-    hipLaunchKernelGGL(ks_inner_blocks_kernel, grid(K * a.T, nb), dim3(256), lds * a.dn, s, d2e, ext, K, a, blkLog,
-                       dte.psi_rev, dte.psi_rev_sh, evk, evk_sh, accQ, accP);
+    hipLaunchKernelGGL(ks_inner_blocks_kernel, ks_grid(K * a.T, nb), dim3(256), lds * a.dn, s, ks.d2e, ks.ext, K, a,
+                       blkLog, dte.psi_rev, dte.psi_rev_sh, evk, evk_sh, ks.accQ, ks.accP);
   }
   SHELFI_HIP(hipGetLastError());
   // ModDown: INTT of the P part, P -> Q_l conversion, its NTT fused with the finish
-  launch_ntt(accP, K * 2 * a.kP, a.kP, a.logN, true, tower_view(dte, a.Ll, N), s);
-  if (fuse_cols) {
-    NTT_DISPATCH_KS(logR, moddown_cols_kernel, grid(K * 2, (uint32_t)((N >> logR) / 256)), dim3(256), 0, s, accP, a,
-                    dtq.psi_rev, dtq.psi_rev_sh, z);
-  } else {
-    hipLaunchKernelGGL(moddown_kernel, grid(K * 2, bpr), dim3(256), 0, s, accP, a, z);
-    SHELFI_HIP(hipGetLastError());
-    launch_ntt_cols(z, K * 2 * a.Ll, a.Ll, a.logN, false, dtq, s);
-  }
-  SHELFI_HIP(hipGetLastError());
-  if (sh > 0 && blkLog == 11 && dtq.red_ok)
-    hipLaunchKernelGGL((ks_finish_blocks_ct<11, 3, 3, 3, 2>), grid(K * 2 * a.Ll, nb), dim3(256), 0, s, z, accQ, a,
-                       dtq.tw_fwd_blk, out);
-  else if (sh > 0 && blkLog == 12 && dtq.red_ok)
-    hipLaunchKernelGGL((ks_finish_blocks_ct<12, 3, 3, 3, 3>), grid(K * 2 * a.Ll, nb), dim3(256), 0, s, z, accQ, a,
-                       dtq.tw_fwd_blk, out);
-  else
-    hipLaunchKernelGGL(ks_finish_blocks_kernel, grid(K * 2 * a.Ll, nb), dim3(256), lds, s, z, accQ, a, blkLog,
-                       dtq.psi_rev, dtq.psi_rev_sh, out);
-  SHELFI_HIP(hipGetLastError());
+  launch_ks_moddown(a, dtq, dte, K, ks.accP, ks.z, s);
+  launch_ks_finish(a, dtq, K, ks.z, ks.accQ, out, s);
 }
 
 // -------------------------------------------------------------- ModReduce ----

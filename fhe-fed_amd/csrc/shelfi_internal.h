@@ -84,6 +84,7 @@ struct Switches {
   uint64_t dot_slice_cts = 256;   // SHELFI_DOT_SLICE_CTS: ciphertexts a slice of EvalInnerProduct (at most 16 slices)
   uint64_t gram_slice_cts = 256;  // SHELFI_GRAM_SLICE_CTS: the same for the Gram matrix, sliced only while its tiles leave the machine idle
   uint64_t dotp_slice_cts = 256;  // SHELFI_DOTP_SLICE_CTS: the same for EvalInnerProduct(ct, pt), also held to the SHELFI_EVAL_CHUNK_MIB budget
+  int hoist_keys = 0;             // SHELFI_HOIST_KEYS_PER_PASS=1..16: rotations a workgroup of the hoisted inner product serves (0: kHoistKeysPerPass)
   uint64_t wavg_chunk_mib = 0;    // SHELFI_WAVG_CHUNK_MIB: bytes-API aggregation chunk per learner group
                                   // (0: 32 MiB per learner with direct uploads, 128 per group through the ring)
   uint64_t stage_slot_mib = 16;   // SHELFI_STAGE_SLOT_MIB: pinned staging-ring slot (DMA granule)
@@ -281,7 +282,7 @@ struct shelfi_ctx {
   int decode_exact = 0;          // shelfi_set_decode_exact: every decrypt over every tower, exact CRT
   uint64_t decode_redo_count = 0;  // decrypt calls whose fast pass was redone exactly (shelfi_decode_redo_count)
   uint64_t encode_redo_count = 0;  // encrypt calls redone on the large-value path (shelfi_encode_redo_count)
-  uint64_t eval_chunk_count = 0;   // launch chains of the last mult / gram / wsum_ct / rescale / rotate / eval_sum (shelfi_eval_chunk_count)
+  uint64_t eval_chunk_count = 0;   // launch chains of the last mult / gram / wsum_ct / rescale / rotate / rotate_many / eval_sum (shelfi_eval_chunk_count)
   uint64_t dot_slice_count = 0;    // slices of the last successful dot (shelfi_dot_slice_count)
   uint64_t gram_slice_count = 0;   // slices of the last successful gram (shelfi_gram_slice_count)
   uint64_t dotp_slice_count = 0;   // slices of the last successful project (shelfi_dotp_slice_count)
@@ -539,6 +540,12 @@ struct KsArgs {
 // out = relinearized (a x b): tensor, ModUp per digit, inner product with the key,
 // ModDown.  a, b, out [K][2][Ll][N] (out may alias a or b); scratch = ks_scratch_bytes(.., K).
 // dtq: tables of Q (prefix Q_l used); dte: Q_l u P; dtf[j]: digit j's foreign towers.
+// towers of ext for one ciphertext: every digit's foreign towers (T minus its own), digit after digit
+inline uint64_t ks_ext_towers(uint32_t Ll, uint32_t kP, uint32_t dn, uint32_t alpha) {
+  uint64_t ext = 0;
+  for (uint32_t j = 0; j < dn; ++j) ext += Ll + kP - std::min(alpha, Ll - j * alpha);
+  return ext;
+}
 size_t ks_scratch_bytes(uint32_t Ll, uint32_t kP, uint32_t dn, uint32_t alpha, uint32_t N, uint64_t K);
 void launch_eval_mult(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte,
                       const DeviceTables* dtf, const uint64_t* evk, const uint64_t* evk_sh, const uint64_t* x,
@@ -621,6 +628,42 @@ void launch_poly_combine(const KsArgs* a, const DeviceTables& dtq, const DeviceT
 void launch_rotate(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,
                    const uint64_t* rk, const uint64_t* rk_sh, uint32_t g, const uint64_t* ct, uint64_t K,
                    uint64_t* out, void* scratch, hipStream_t s);
+// launch_key_switch's stages, for the calls that batch them differently (hoist.hip): the INTT columns of
+// d2c [K][Ll][N] and ModUp into ext; ModDown of accP [K][2][kP][N] into z [K][2][Ll][N]; the finish
+// out [K][2][Ll][N] += (accQ - NTT(z)) P^-1.
+void launch_ks_modup(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const DeviceTables* dtf,
+                     uint64_t K, uint64_t* d2c, uint64_t* ext, hipStream_t s);
+void launch_ks_moddown(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, uint64_t K, uint64_t* accP,
+                       uint64_t* z, hipStream_t s);
+void launch_ks_finish(const KsArgs& a, const DeviceTables& dtq, uint64_t K, const uint64_t* z, const uint64_t* accQ,
+                      uint64_t* out, hipStream_t s);
+// Hoisted rotations (hoist.hip): one decomposition of c1 serves every rotation of the call.
+// A group is the rotations in flight behind one decomposition: their keys (the evaluation key's layout), Galois
+// elements with their inverses mod 2N, and outputs [K][2][Ll][N], by value in the kernel arguments.
+constexpr int kHoistMaxGroup = 16;
+constexpr int kHoistKeysPerPass = 4;  // rotations one workgroup serves behind its one NTT pass (4 against 1, 2, 8 and 16: DESIGN.md §2.21)
+struct HoistRot {
+  const uint64_t* key;
+  const uint64_t* key_sh;
+  uint64_t* out;
+  uint32_t g, ginv;
+};
+struct HoistGroup {
+  HoistRot r[kHoistMaxGroup];
+  uint32_t n;
+};
+// scratch of a chain of K ciphertexts with n rotations in flight: hoist_shared_bytes (d2e | d2c | ext, rounded
+// up to 64 bytes) + n * hoist_acc_bytes (accQ | accP | z)
+size_t hoist_shared_bytes(const KsArgs& a, uint64_t K);
+size_t hoist_acc_bytes(const KsArgs& a, uint64_t K);
+// the decomposition of ct [K][2][Ll][N]'s c1 into the scratch's shared part
+void launch_hoist_decompose(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte,
+                            const DeviceTables* dtf, const uint64_t* ct, uint64_t K, void* scratch, hipStream_t s);
+// ... and behind it grp.r[i].out = (sigma_g(c0), 0) + ModDown(sum_j sigma_g(D_j) (.) key_j) for the group's
+// rotations; no output overlaps ct.  out_contiguous: grp.r[i].out = grp.r[0].out + i * K * 2 * Ll * N, so the
+// finish runs as one batch.
+void launch_hoist_rotations(const KsArgs& a, const DeviceTables& dtq, const DeviceTables& dte, const HoistGroup& grp,
+                            bool out_contiguous, const uint64_t* ct, uint64_t K, void* scratch, hipStream_t s);
 // EvalAdd of two ciphertext batches: out = a + b mod q_t over rows = K * 2 * Ll polynomials (out may
 // be a or b)
 void launch_ct_add(const uint64_t* a, const uint64_t* b, uint64_t rows, uint32_t Ll, uint32_t logN,

@@ -60,6 +60,7 @@ void reload_switches() {
     if (atoll(e) > 0) s.gram_slice_cts = (uint64_t)atoll(e);
   if (const char* e = getenv("SHELFI_DOTP_SLICE_CTS"))
     if (atoll(e) > 0) s.dotp_slice_cts = (uint64_t)atoll(e);
+  s.hoist_keys = env_choice("SHELFI_HOIST_KEYS_PER_PASS", {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16}, 0);
   if (const char* e = getenv("SHELFI_WAVG_CHUNK_MIB"))
     if (atoll(e) > 0) s.wavg_chunk_mib = (uint64_t)atoll(e);
   if (const char* e = getenv("SHELFI_STAGE_SLOT_MIB"))

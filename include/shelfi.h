@@ -613,6 +613,26 @@ int shelfi_set_rotation_key(shelfi_ctx* ctx, int32_t index, const uint64_t* key)
  * is a copy; out may then be ct).  Scale and depth are the input's. */
 int shelfi_dev_rotate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, int32_t index,
                       uint64_t* out_dev, void* stream);
+/* R rotations of the same ciphertexts from ONE digit decomposition (hoisting: PALISADE's
+ * EvalFastRotationPrecompute / EvalFastRotation).  With D_j digit j of c1 over Q_l u P in
+ * EVALUATION form -- the decomposition shelfi_dev_rotate makes of sigma_g(c1), here made of c1 itself, once --
+ * and g_r the Galois element of indices[r]:
+ *   out[r] = (sigma_{g_r}(c0), 0) + ModDown(sum_j sigma_{g_r}(D_j) (.) key_{r,j})
+ * under the same rotation keys shelfi_dev_rotate uses.  out_dev [R][K][2][towers][N]: every out[r] an ordinary
+ * batch at the input's scale and depth.  out[r] decrypts to the slots shelfi_dev_rotate(.., indices[r], ..)
+ * gives, within noise, but is NOT bit-equal to it: the approximate basis conversion does not commute with
+ * sigma_g.  Indices may repeat; index 0 is a copy of the input.  R = 1..64; R = 0 or K = 0 enqueues nothing.
+ * Every key is looked up before anything is enqueued: a missing one is SHELFI_ERR_STATE ("no rotation key for
+ * index r") with out_dev untouched.  A NULL pointer, towers outside 1..L, |index| >= batch, R > 64, out_dev
+ * overlapping ct_dev, and a chain with num_towers + special primes > 16 (before any key lookup):
+ * SHELFI_ERR_ARG.  The K ciphertexts are cut into launch chains under SHELFI_EVAL_CHUNK_MIB, and a list whose
+ * accumulators (one set per rotation in flight) would not fit beside one ciphertext's decomposition is cut into
+ * rotation groups as well; shelfi_eval_chunk_count reports chains x groups, and no output bit depends on either.
+ * The floor of both cuts is one ciphertext with one rotation in flight: where that alone needs more than the budget
+ * (its decomposition plus one accumulator set), the chain runs at that size, over the budget, exactly as a
+ * one-ciphertext chain of shelfi_dev_rotate does -- the budget bounds the batching, never refuses a call. */
+int shelfi_dev_rotate_many(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint32_t towers, const int32_t* indices,
+                           size_t R, uint64_t* out_dev, void* stream);
 /* cc->EvalSum(ct, n) (mkhe.cpp:372), n a power of two in 1..batch: log2(n) steps
  * acc <- acc + Rotate(acc, 2^i), i = 0 .. log2(n) - 1; slot i then holds
  * sum_{j < n} x[(i + j) mod batch].  n = 1 is a copy.  ct_dev and out_dev must not overlap. */
@@ -632,7 +652,7 @@ int shelfi_dev_conjugate(shelfi_ctx* ctx, const uint64_t* ct_dev, size_t K, uint
                          void* stream);
 /* The number of launch chains (chunks of the batch, each within the SHELFI_EVAL_CHUNK_MIB scratch budget,
  * 2048 by default) the last successful shelfi_dev_mult, shelfi_dev_gram, shelfi_dev_wsum_ct, shelfi_dev_rescale,
- * shelfi_dev_rotate, shelfi_dev_conjugate or shelfi_dev_eval_sum on this context took.  0 after a call that enqueued no chain (K = 0, index 0,
+ * shelfi_dev_rotate, shelfi_dev_rotate_many, shelfi_dev_conjugate or shelfi_dev_eval_sum on this context took.  0 after a call that enqueued no chain (K = 0, index 0,
  * n = 1); a refused call leaves it unchanged.  For tests of the chunking. */
 uint64_t shelfi_eval_chunk_count(const shelfi_ctx* ctx);
 /* cc->EvalAdd(ct_a, ct_b) (mkhe.cpp:168, :368): out = a + b mod q_t over [K][2][towers][N]; out may be a
